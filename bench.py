@@ -7,7 +7,13 @@ fp32, nlist=4096, nprobe=32, batch=1024, k=10 (cfg C; `config.workload`) —
 through the product C-ABI (dg_search_device), queries resident in HBM when
 the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up the index, warms up, times the K steps and prints the
+result line.  --full adds everything else the benchmark reports: averaged
+per-stage/roofline figures from extra untimed steps, recall@k against the
+exact sweep, the CPU baseline with its cross-engine recall, and (with
+--recall-curve) the nprobe operating curve.  --dump-outputs DIR writes the
+(distances, ids) the last timed step returned as DIR/<name>.npy.
 N>1 is launched by the driver via torch.distributed.run, one rank per GPU
 over RCCL: the database is row-sharded across ranks with replicated
 centroids; each step is local IVF search + RCCL all-gather of per-rank
@@ -16,8 +22,8 @@ top-k over xGMI + device-side merge.  scaling is
 
 Data: synthetic, generated on-device per chunk with seeded torch
 generators (protocol in DESIGN.md §data; identical across ranks and across
-the GPU/CPU legs of one run).  The CPU baseline (rank 0, N=1) times the
-oracle's vectorized IVF search on the same structure/host cores — the
+the GPU/CPU legs of one run).  The CPU baseline (--full; rank 0, N=1) times
+the oracle's vectorized IVF search on the same structure/host cores — the
 checker timed as a baseline, never the product path.
 """
 import argparse
@@ -291,6 +297,31 @@ def read_traffic(workload_name):
     return None
 
 
+DUMP_MAX_BYTES = 64 << 20  # cap on everything --dump-outputs writes
+
+
+def dump_outputs(outdir, dist, ids, max_bytes=DUMP_MAX_BYTES):
+    """Write what the last timed step returned to its caller — the [nq, k]
+    distances and ids — as outdir/distances.npy (float32) and outdir/ids.npy
+    (float64; ids are < 2^53 so the conversion is exact).  An output larger
+    than max_bytes is cut to a fixed seeded sample of its query rows, whose
+    indices go to outdir/rows.npy (float64)."""
+    os.makedirs(outdir, exist_ok=True)
+    d = dist.detach().cpu().numpy().astype(np.float32)
+    i = ids.detach().cpu().numpy().astype(np.float64)
+    nq, k = d.shape
+    hdr = 3 * 128  # .npy headers
+    row_bytes = k * (4 + 8) + 8
+    if nq * row_bytes + hdr > max_bytes:
+        keep = max(1, (max_bytes - hdr) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep,
+                                                       replace=False))
+        d, i = d[rows], i[rows]
+        np.save(os.path.join(outdir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(outdir, "distances.npy"), d)
+    np.save(os.path.join(outdir, "ids.npy"), i)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -308,13 +339,25 @@ def main():
     ap.add_argument("--m", type=int, default=96)  # cfg D subquantizers
     ap.add_argument("--quick", action="store_true",
                     help="reduced size for smoke runs (1M rows)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-recall", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: averaged"
+                         " per-stage stats, recall@k, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's distances and ids to"
+                         " DIR/distances.npy and DIR/ids.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-recall", action="store_true",
+                    help="with --full: skip recall@k")
     ap.add_argument("--recall-curve", action="store_true",
                     help="also sweep nprobe in {32,64,128,256} and write the"
                          " QPS-vs-recall operating curve to"
                          " gpurun_out/recall_curve.json")
     args = ap.parse_args()
+    if args.recall_curve and not args.full:
+        ap.error("--recall-curve needs --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.quick:
         args.n, args.nlist = 1_000_000, 1024
 
@@ -350,7 +393,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.time()
     for _ in range(args.steps):
-        merged_step(idx, q, k, nprobe, dist_t, ids_t, world, bufs)
+        out_d, out_i = merged_step(idx, q, k, nprobe, dist_t, ids_t, world,
+                                   bufs)
     idx.sync()
     torch.cuda.synchronize()
     if world > 1:
@@ -361,11 +405,16 @@ def main():
         torch.distributed.all_reduce(e, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(e.item())
 
-    # ---- per-stage stats from extra untimed steps (hipEvent timings on the
-    # library stream; torch events would miss it)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_d, out_i)
+
+    # ---- per-stage stats (hipEvent timings on the library stream; torch
+    # events would miss it): the last timed step's own figures in a plain
+    # run, the mean over extra untimed steps with --full
     scan_ms, coarse_ms, total_ms, alg_bytes = [], [], [], []
-    for _ in range(5):
-        merged_step(idx, q, k, nprobe, dist_t, ids_t, world, bufs)
+    for _ in range(5 if args.full else 1):
+        if args.full:
+            merged_step(idx, q, k, nprobe, dist_t, ids_t, world, bufs)
         st = idx.stats()
         scan_ms.append(st["last_scan_ms"])
         coarse_ms.append(st["last_coarse_ms"])
@@ -373,13 +422,13 @@ def main():
         alg_bytes.append(st["last_scan_bytes_algorithmic"])
 
     recall = 1.0 if args.kind == "flat" else None  # Flat IS the exact scan
-    if not args.no_recall and args.kind == "ivf_flat":
+    if args.full and not args.no_recall and args.kind == "ivf_flat":
         # (PQ exact-sweep GT at cfg D would need a 3.2 TB candidate buffer;
         # PQ recall is covered by the parity tests at tractable sizes)
         recall = compute_recall(idx, q, k, nprobe, args.nlist, world, device)
 
     cpu = None
-    if (rank == 0 and world == 1 and not args.no_cpu_baseline
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
             and args.kind in ("ivf_flat", "flat")):
         q_host = q.cpu().numpy()
         try:
@@ -427,6 +476,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1000, 3),
             "higher_is_better": True,
             "scaling": "strong",
