@@ -79,6 +79,13 @@ static dg_status dbuf_reserve(dg_dbuf& b, size_t bytes, hipStream_t s,
   return DG_OK;
 }
 
+// DG_SCAN_FUSED=0 forces the store-all-candidates IVF-Flat scan (A/B and
+// tests); read per call so one process can run both paths.
+static bool scan_fused_enabled() {
+  const char* e = getenv("DG_SCAN_FUSED");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
 static void dbuf_free(dg_dbuf& b) {
   if (b.p) (void)hipFree(b.p);
   b = {};
@@ -342,7 +349,7 @@ extern "C" void dg_index_destroy(dg_index* ix) {
         &ix->d_cb_norms, &ix->ws_T, &ix->ws_Tf32, &ix->ws_queries, &ix->ws_qnorms,
         &ix->ws_dots, &ix->ws_probes, &ix->ws_inv, &ix->ws_cand, &ix->ws_units,
         &ix->ws_small, &ix->ws_topk, &ix->ws_scan, &ix->ws_seg, &ix->ws_gq,
-        &ix->ws_gout, &ix->ws_bm})
+        &ix->ws_gout, &ix->ws_bm, &ix->ws_partial})
     dbuf_free(*b);
   if (ix->graph_exec) (void)hipGraphExecDestroy(ix->graph_exec);
   for (auto& e : ix->ev)
@@ -1087,10 +1094,12 @@ static dg_status finalize_csr(dg_index* ix) {
     std::vector<int64_t> chunk_base;
     std::vector<uint32_t> all_units;
     int64_t t_elems = 0;
+    int32_t cpl_max = 0;
     for (int32_t l = 0; l < nlist; l++) {
       int64_t len = ix->h_csr_offsets[l + 1] - ix->h_csr_offsets[l];
       int32_t nch = (int32_t)((len + CR - 1) / CR);
       chunk_off[l + 1] = chunk_off[l] + nch;
+      cpl_max = std::max(cpl_max, nch);
       for (int32_t c = 0; c < nch; c++) {
         int32_t nrows = (int32_t)std::min<int64_t>(CR, len - (int64_t)c * CR);
         int32_t pad = (nrows + 3) & ~3;
@@ -1101,6 +1110,7 @@ static dg_status finalize_csr(dg_index* ix) {
       }
     }
     ix->total_chunks = chunk_off[nlist];
+    ix->cpl_max = cpl_max;
     size_t meta_bytes = ((size_t)nlist + 1) * 4 +
                         (size_t)ix->total_chunks * 8 +
                         (size_t)ix->total_chunks * 8;
@@ -1555,9 +1565,6 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     dgk::init_cursors(ix->stream, inv_offsets64, nlist, cursors);
     dgk::scatter_probes(ix->stream, probes, nq, np, nullptr, cursors, inv_q,
                         inv_rank);
-    dgk::cand_offsets(ix->stream, probes, nq, np,
-                      (const int64_t*)ix->d_csr_offsets.p, qp_off, q_total);
-    dgk::excl_scan_i64(ix->stream, q_total, nq, q_cand_base, sscr);
     const int32_t chunk_rows = dg_index::kChunkRows;
     // candidate buffer sized from the HOST upper bound (nq x sum of the
     // np longest lists, finalize's sorted prefix) and the scan launched
@@ -1565,10 +1572,35 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     // lists) — no mid-search device readback / stream sync.
     const int64_t ub_cand =
         nq * ix->h_len_prefix_desc[std::min<int32_t>(np, nlist)];
-    if ((st = dbuf_reserve(ix->ws_cand,
-                           (size_t)std::max<int64_t>(ub_cand, 1) * 8,
-                           ix->stream, false)) != DG_OK) {
-      return st;
+    // IVF-Flat top-k: the scan keeps k candidates per wave in fixed slots
+    // ([nq][np][cpl_max][waves/chunk][k], preset empty) instead of storing
+    // all of them, so the dense candidate offsets and ws_cand are not
+    // needed.  A list so long that the slots would outgrow the candidate
+    // buffer they replace keeps the unfused path, as does DG_SCAN_FUSED=0
+    // (A/B switch, read per call like DG_NO_GRAPH).
+    const int64_t partial_per_q =
+        (int64_t)np * ix->cpl_max * (chunk_rows / 256) * k;
+    const bool fused = !is_pq && !rr && k <= dg_index::kScanFuseMaxK &&
+                       nq * partial_per_q <= ub_cand && scan_fused_enabled();
+    ix->last_scan_fused = fused;
+    if (fused) {
+      if ((st = dbuf_reserve(ix->ws_partial,
+                             (size_t)std::max<int64_t>(nq * partial_per_q, 1) *
+                                 8,
+                             ix->stream, false)) != DG_OK) {
+        return st;
+      }
+      (void)hipMemsetAsync(ix->ws_partial.p, 0xff,
+                           (size_t)nq * partial_per_q * 8, ix->stream);
+    } else {
+      dgk::cand_offsets(ix->stream, probes, nq, np,
+                        (const int64_t*)ix->d_csr_offsets.p, qp_off, q_total);
+      dgk::excl_scan_i64(ix->stream, q_total, nq, q_cand_base, sscr);
+      if ((st = dbuf_reserve(ix->ws_cand,
+                             (size_t)std::max<int64_t>(ub_cand, 1) * 8,
+                             ix->stream, false)) != DG_OK) {
+        return st;
+      }
     }
     char* cm = (char*)ix->d_chunk_meta.p;
     const uint32_t* units =
@@ -1632,13 +1664,22 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           (const int64_t*)(mp + ((size_t)nlist + 1) * 4);
       const int32_t mean_probes =
           (int32_t)((nq * (int64_t)np) / std::max(1, nlist));
-      dgk::ivf_scan_col(ix->stream, units, total_units,
-                        (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
-                        d_chunk_base, (const float*)ix->d_csr_t.p,
-                        (const float*)ix->d_csr_vnorms.p, dq, d,
-                        inv_offsets32, inv_q, inv_rank, qp_off, q_cand_base,
-                        np, metric, d_bitmap, chunk_rows,
-                        (uint64_t*)ix->ws_cand.p, mean_probes);
+      if (fused)
+        dgk::ivf_scan_topk(ix->stream, units, total_units,
+                           (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
+                           d_chunk_base, (const float*)ix->d_csr_t.p,
+                           (const float*)ix->d_csr_vnorms.p, dq, d,
+                           inv_offsets32, inv_q, inv_rank, np, metric,
+                           d_bitmap, chunk_rows, k, ix->cpl_max,
+                           (uint64_t*)ix->ws_partial.p);
+      else
+        dgk::ivf_scan_col(ix->stream, units, total_units,
+                          (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
+                          d_chunk_base, (const float*)ix->d_csr_t.p,
+                          (const float*)ix->d_csr_vnorms.p, dq, d,
+                          inv_offsets32, inv_q, inv_rank, qp_off, q_cand_base,
+                          np, metric, d_bitmap, chunk_rows,
+                          (uint64_t*)ix->ws_cand.p, mean_probes);
     }
     if (!ix->capturing) (void)hipEventRecord(ix->ev[3], ix->stream);
 
@@ -1666,9 +1707,16 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
       ix->times.last_nq = nq;
       return st;
     }
-    // select + emit
-    dgk::select_u64(ix->stream, (const uint64_t*)ix->ws_cand.p, q_cand_base,
-                    q_total, nq, k, final_tk, k);
+    // select + emit (fused: merge of the per-wave slots, uniform segments)
+    if (fused) {
+      dgk::fill_base_total(ix->stream, nq, partial_per_q, q_cand_base,
+                           q_total);
+      dgk::select_u64(ix->stream, (const uint64_t*)ix->ws_partial.p,
+                      q_cand_base, q_total, nq, k, final_tk, k);
+    } else {
+      dgk::select_u64(ix->stream, (const uint64_t*)ix->ws_cand.p, q_cand_base,
+                      q_total, nq, k, final_tk, k);
+    }
     dgk::emit_results(ix->stream, final_tk, (const int64_t*)ix->d_csr_ids.p,
                       dqn, nq, k, metric, metric == DG_METRIC_L2 ? 1 : 0,
                       d_out_dist, d_out_ids);
@@ -1738,9 +1786,10 @@ extern "C" dg_status dg_search_device(dg_index* ix, int64_t nq,
     const size_t q_bytes = (size_t)nq * ix->d_user * 4;
     const size_t dist_bytes = (size_t)nq * k * 4;
     const size_t ids_bytes = (size_t)nq * k * 8;
+    const bool fused_now = scan_fused_enabled();  // captured into the graph
     if (ix->graph_exec && ix->graph_nq == (int32_t)nq &&
         ix->graph_k == k && ix->graph_np == nprobe &&
-        ix->graph_gen == gen) {
+        ix->graph_fused == fused_now && ix->graph_gen == gen) {
       DG_HIP_CHECK(hipMemcpyAsync(ix->ws_gq.p, d_x, q_bytes,
                                   hipMemcpyDeviceToDevice, ix->stream));
       DG_HIP_CHECK(hipGraphLaunch(ix->graph_exec, ix->stream));
@@ -1786,6 +1835,7 @@ extern "C" dg_status dg_search_device(dg_index* ix, int64_t nq,
           ix->graph_nq = (int32_t)nq;
           ix->graph_k = k;
           ix->graph_np = nprobe;
+          ix->graph_fused = fused_now;
           // capture itself allocates nothing (warm run sized buffers),
           // so gen2 still describes the captured pointers
           ix->graph_gen = gen2;
@@ -2116,6 +2166,12 @@ extern "C" void dg_unlock_write(dg_index* ix) {
 }
 
 // ---------------- stats ----------------
+extern "C" int dg_last_scan_fused(dg_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard sg(ix->search_mu);
+  return ix->last_scan_fused ? 1 : 0;
+}
+
 extern "C" dg_status dg_stats(dg_index* ix, dg_stats_out* out) {
   if (!ix || !out) return DG_EINVAL;
   std::shared_lock lk(ix->rw);

@@ -114,6 +114,11 @@ struct dg_index {
                             // + all-chunks unit array u32[2*nchunks]
   int32_t total_chunks = 0;
   static constexpr int32_t kChunkRows = 1024;
+  // IVF-Flat top-k: the scan keeps each wave's k smallest candidates when
+  // k <= kScanFuseMaxK (one result lane per rank, so at most 64); larger k
+  // stores every candidate (DESIGN.md §Kernels has the measurement)
+  static constexpr int32_t kScanFuseMaxK = 64;
+  int32_t cpl_max = 0;      // 1024-row chunks of the longest list
 
   // Flat uses d_csr_* with a single implicit list (nlist=1) so scan/select
   // machinery is shared.
@@ -149,6 +154,9 @@ struct dg_index {
   // per-row pass bitmap (filters/tombstones) — index-owned so captured
   // graphs may reference it (see search_core)
   dg_dbuf ws_bm;
+  // per-wave top-k slots of the fused IVF-Flat scan (replaces ws_cand there)
+  dg_dbuf ws_partial;
+  bool last_scan_fused = false;  // path of the last search_core IVF scan
 
   // timing
   hipEvent_t ev[12] = {};
@@ -161,6 +169,7 @@ struct dg_index {
   // when (nq, k, nprobe) match and the index generation is unchanged.
   hipGraphExec_t graph_exec = nullptr;
   int32_t graph_nq = 0, graph_k = 0, graph_np = 0;
+  bool graph_fused = false;  // DG_SCAN_FUSED state the graph was captured in
   uint64_t graph_gen = 0;   // generation the graph was captured at
   uint64_t index_gen = 1;   // bumped on finalize/mutation/buffer growth
   dg_dbuf ws_gq, ws_gout;   // fixed staging: queries in, dist+ids out
@@ -237,6 +246,18 @@ void ivf_scan_col(hipStream_t s, const uint32_t* units, int32_t n_units,
                   const int64_t* q_cand_base, int32_t nprobe, int metric,
                   const uint32_t* bitmap, int32_t chunk_rows, uint64_t* cand,
                   int32_t mean_probes);
+// IVF-Flat top-k scan with the per-wave selection fused in: writes the k
+// (<= dg_index::kScanFuseMaxK) smallest candidates of each wave to
+// partial[nq][nprobe][cpl_max][chunk_rows/256][k]; the caller presets
+// partial to 0xff bytes (empty) and merges it with select_u64.
+void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
+                   const int64_t* csr_offsets, const int32_t* chunk_off,
+                   const int64_t* chunk_base, const float* tvec,
+                   const float* vnorms, const float* queries, int32_t d,
+                   const int32_t* inv_offsets, const int32_t* inv_q,
+                   const int32_t* inv_rank, int32_t nprobe, int metric,
+                   const uint32_t* bitmap, int32_t chunk_rows, int32_t k,
+                   int32_t cpl_max, uint64_t* partial);
 void transpose_chunks(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int64_t* csr_offsets, const int32_t* chunk_off,
                       const int64_t* chunk_base, const float* rowmajor,

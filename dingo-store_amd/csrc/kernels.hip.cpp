@@ -960,16 +960,134 @@ typedef float dg_f4 __attribute__((ext_vector_type(4)));
       DG_WAITV(n, b);                                               \
   } while (0)
 
+// ---------- fused per-wave top-k epilogue (IVF-Flat top-k path) ----------
+// Instead of storing every candidate and re-reading all of them in
+// k_select_u64, the scan keeps only each wave's kf smallest candidates per
+// staged query.  The top-k of a union is the top-k of the per-subset
+// top-k's and packed candidates are unique per query (row in the low 32
+// bits), so the later merge over the partial slots is bit-identical to a
+// select over all candidates.
+
+// min over the 64 lanes, returned wave-uniform.  DPP ladder: two quad
+// permutes, half-mirror, mirror (each 16-lane row now uniform), then the
+// gfx9 row broadcasts fold the four rows into lane 63.  Needs the whole
+// wave converged.  Rows masked out of a step read the min identity (~0),
+// which also lets the compiler fold each step into one v_min_u32_dpp.
+__device__ __forceinline__ uint32_t dg_wave_min_u32(uint32_t v) {
+#define DG_DPP(ctrl, rows)                                                 \
+  ((uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, (ctrl), (rows), 0xf, \
+                                         false))
+  v = min(v, DG_DPP(0xB1, 0xf));   // quad_perm [1,0,3,2]
+  v = min(v, DG_DPP(0x4E, 0xf));   // quad_perm [2,3,0,1]
+  v = min(v, DG_DPP(0x141, 0xf));  // row_half_mirror
+  v = min(v, DG_DPP(0x140, 0xf));  // row_mirror
+  v = min(v, DG_DPP(0x142, 0xa));  // row_bcast15 into rows 1,3
+  v = min(v, DG_DPP(0x143, 0xc));  // row_bcast31 into rows 2,3
+#undef DG_DPP
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// Select the wave's kf (<= 64) smallest candidates of each staged query
+// from the lane's 4 accumulators and write them, ascending, to
+// partial[cbase[j] + wslot .. + kf); unused tail entries are kCandEmpty.
+// Extract-min on the 32-bit key; among equal keys the lowest lane, then the
+// lowest x wins, which is the smaller row — the u64 order.  The one key
+// value that a real candidate shares with kCandEmpty (0xffffffff, a NaN
+// encoding) takes a plain u64 extract-min instead.
+// Must be entered by ALL 64 lanes; lanes without rows pass rr0 >= nrows.
+template <int JT>
+__device__ __forceinline__ void dg_scan_topk_epilogue(
+    const float (&acc)[JT][4], const int64_t* cbase, int64_t wslot,
+    const float* __restrict__ vnorms, int32_t nrows, int32_t rr0,
+    int64_t row0, int32_t qt, int metric, const uint32_t* __restrict__ bitmap,
+    int32_t kf, uint64_t* __restrict__ partial) {
+  constexpr int RPL = 4;
+  const int lane = threadIdx.x % WAVE;
+  const uint32_t rlo = (uint32_t)(row0 + rr0);
+  bool ok[RPL];
+  float vn[RPL];
+#pragma unroll
+  for (int x = 0; x < RPL; x++) {
+    ok[x] = rr0 + x < nrows;
+    vn[x] = 0.f;
+    if (ok[x]) {
+      const int64_t r = row0 + rr0 + x;
+      if (bitmap) ok[x] = (bitmap[r >> 5] >> (r & 31)) & 1;
+      if (metric == 0) vn[x] = vnorms[r];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < JT; j++) {
+    if (j < qt) {
+      uint32_t kx[RPL];
+      bool odd = false;
+#pragma unroll
+      for (int x = 0; x < RPL; x++) {
+        float key = (metric == 0) ? vn[x] - 2.0f * acc[j][x] : -acc[j][x];
+        const uint32_t e = enc_f32(key);
+        odd |= ok[x] && e == 0xffffffffu;
+        kx[x] = ok[x] ? e : 0xffffffffu;
+      }
+      uint32_t res_hi = 0xffffffffu, res_lo = 0xffffffffu;
+      if (__ballot(odd) == 0) {
+        for (int32_t rnd = 0; rnd < kf; rnd++) {
+          const uint32_t m = min(min(kx[0], kx[1]), min(kx[2], kx[3]));
+          const uint32_t wm = dg_wave_min_u32(m);
+          if (wm == 0xffffffffu) break;  // only empties left
+          const int L = __builtin_ctzll(__ballot(m == wm));
+          const uint32_t c =
+              kx[0] == wm ? 0u : kx[1] == wm ? 1u : kx[2] == wm ? 2u : 3u;
+          const uint32_t row =
+              (uint32_t)__builtin_amdgcn_readlane((int)(rlo + c), L);
+          const uint32_t sel = (lane == L) ? c : (uint32_t)RPL;
+#pragma unroll
+          for (int x = 0; x < RPL; x++)
+            kx[x] = (sel == (uint32_t)x) ? 0xffffffffu : kx[x];
+          if (lane == rnd) {
+            res_hi = wm;
+            res_lo = row;
+          }
+        }
+      } else {
+        uint64_t cv[RPL];
+#pragma unroll
+        for (int x = 0; x < RPL; x++)
+          cv[x] = ok[x] ? (((uint64_t)kx[x] << 32) | (rlo + (uint32_t)x))
+                        : kCandEmpty;
+        for (int32_t rnd = 0; rnd < kf; rnd++) {
+          uint64_t m = min(min(cv[0], cv[1]), min(cv[2], cv[3]));
+          for (int off = 32; off; off >>= 1)
+            m = min(m, (uint64_t)__shfl_xor((long long)m, off, WAVE));
+          if (m == kCandEmpty) break;
+#pragma unroll
+          for (int x = 0; x < RPL; x++)
+            if (cv[x] == m) cv[x] = kCandEmpty;
+          if (lane == rnd) {
+            res_hi = (uint32_t)(m >> 32);
+            res_lo = (uint32_t)m;
+          }
+        }
+      }
+      if (lane < kf)
+        partial[cbase[j] + wslot + lane] = ((uint64_t)res_hi << 32) | res_lo;
+    }
+  }
+}
+
 // row-scan body of k_ivf_scan_pipe, templated on the EFFECTIVE query-tile
 // width JT: tiles that fill at most half the QTM slots take the JT=QTM/2
 // instantiation and skip the zero-padded FMAs (at cfg C the mean tile
 // holds ~8 of 16 queries — half the compute multiplies zeros otherwise).
-template <int JT, bool SAFE>
+// FUSED: every lane of the wave enters, rows or not, and the store of all
+// candidates is replaced by dg_scan_topk_epilogue writing kf per wave at
+// cbase[j] + wslot.
+template <int JT, bool SAFE, bool FUSED = false>
 __device__ __forceinline__ void dg_scan_rows_body(
     const float* smem, const int64_t* cbase, const float* col,
     const float* __restrict__ vnorms, int32_t d, int32_t nrows,
     int32_t nrows_pad, int32_t rr0, int64_t row0, int32_t qt, int metric,
-    const uint32_t* __restrict__ bitmap, uint64_t* __restrict__ cand) {
+    const uint32_t* __restrict__ bitmap, uint64_t* __restrict__ cand,
+    int32_t kf = 0, int64_t wslot = 0) {
   constexpr int RPL = 4;
   constexpr int U = 4;
   float acc[JT][RPL];
@@ -982,7 +1100,10 @@ __device__ __forceinline__ void dg_scan_rows_body(
   // track ONLY this loop's column loads
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  const char* colp = (const char*)(col + rr0);
+  // FUSED lanes past the chunk's rows re-read the chunk's first rows (no
+  // new cache lines) and their sums are discarded by the epilogue
+  const char* colp =
+      (const char*)(col + ((!FUSED || rr0 < nrows_pad) ? rr0 : 0));
   const size_t cstride = (size_t)nrows_pad * 4;  // bytes per dim column
   dg_f4 b0[U], b1[U], b2[U], b3[U];
   auto issue = [&](dg_f4 (&b)[U], int32_t ib) {
@@ -1042,6 +1163,11 @@ __device__ __forceinline__ void dg_scan_rows_body(
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
+  if (FUSED) {
+    dg_scan_topk_epilogue<JT>(acc, cbase, wslot, vnorms, nrows, rr0, row0, qt,
+                              metric, bitmap, kf, cand);
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < JT; j++) {
     if (j < qt) {
@@ -1166,7 +1292,13 @@ __device__ __forceinline__ void dg_scan_rows_body2(
   }
 }
 
-template <int QTM, bool SAFE = false>
+// FUSED (IVF-Flat top-k path): `cand` is the partial-slot buffer
+//   [nq][nprobe][cpl_max][chunk_rows/256][kf]
+// (cpl_max = chunks of the longest list); each wave writes its kf smallest
+// per staged query, every (q, rank, chunk, wave) slot is written at most
+// once and the host presets the buffer to kCandEmpty.  qp_off and
+// q_cand_base are unused.
+template <int QTM, bool SAFE = false, bool FUSED = false>
 __global__ void __launch_bounds__(256, 1) k_ivf_scan_pipe(
     const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
     const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
@@ -1176,7 +1308,7 @@ __global__ void __launch_bounds__(256, 1) k_ivf_scan_pipe(
     const int32_t* __restrict__ inv_rank, const int64_t* __restrict__ qp_off,
     const int64_t* __restrict__ q_cand_base, int32_t nprobe, int metric,
     const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
-    uint64_t* __restrict__ cand) {
+    uint64_t* __restrict__ cand, int32_t kf = 0, int32_t cpl_max = 0) {
   constexpr int RPL = 4;  // rows per lane (float4 column loads)
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [QTM * d]
   int64_t* cbase = (int64_t*)(smem + (size_t)QTM * d);          // [QTM]
@@ -1214,26 +1346,34 @@ __global__ void __launch_bounds__(256, 1) k_ivf_scan_pipe(
       if (j < qt) {
         int32_t q = inv_q[iq0 + t0 + j];
         int32_t rank = inv_rank[iq0 + t0 + j];
-        cbase[j] = q_cand_base[q] + qp_off[(int64_t)q * nprobe + rank] -
-                   list_start;
+        if (FUSED)
+          cbase[j] = ((((int64_t)q * nprobe + rank) * cpl_max + chunk) *
+                      (chunk_rows / (WAVE * RPL))) * kf;
+        else
+          cbase[j] = q_cand_base[q] + qp_off[(int64_t)q * nprobe + rank] -
+                     list_start;
       } else {
         cbase[j] = 0;
       }
     }
     __syncthreads();
 
+    // rb is wave-uniform: a wave either runs a row block whole (FUSED: all
+    // 64 lanes, so the epilogue's cross-lane steps see a converged wave) or
+    // skips it, leaving its slot at the preset kCandEmpty
     for (int32_t rb = wave_id * WAVE * RPL; rb < nrows_pad;
          rb += 4 * WAVE * RPL) {
       const int32_t rr0 = rb + lane * RPL;
-      if (rr0 >= nrows_pad) continue;
+      if (!FUSED && rr0 >= nrows_pad) continue;
+      const int64_t wslot = (int64_t)(rb / (WAVE * RPL)) * kf;
       if (QTM >= 16 && qt <= QTM / 2)
-        dg_scan_rows_body<(QTM >= 16 ? QTM / 2 : QTM), SAFE>(
+        dg_scan_rows_body<(QTM >= 16 ? QTM / 2 : QTM), SAFE, FUSED>(
             smem, cbase, col, vnorms, d, nrows, nrows_pad, rr0, row0, qt,
-            metric, bitmap, cand);
+            metric, bitmap, cand, kf, wslot);
       else
-        dg_scan_rows_body<QTM, SAFE>(smem, cbase, col, vnorms, d, nrows,
-                                     nrows_pad, rr0, row0, qt, metric,
-                                     bitmap, cand);
+        dg_scan_rows_body<QTM, SAFE, FUSED>(smem, cbase, col, vnorms, d,
+                                            nrows, nrows_pad, rr0, row0, qt,
+                                            metric, bitmap, cand, kf, wslot);
     }
   }
 }
@@ -2382,7 +2522,7 @@ void ivf_scan_col(hipStream_t s, const uint32_t* units, int32_t n_units,
                        csr_offsets, chunk_off, chunk_base, tvec, vnorms,    \
                        queries, d, inv_offsets, inv_q, inv_rank, qp_off,    \
                        q_cand_base, nprobe, metric, bitmap, chunk_rows,     \
-                       cand);                                               \
+                       cand, 0, 0);                                         \
   } while (0)
       (void)mean_probes;  // dense-batch 20/24-query tiles fail the
                           // in-flight hazard scan (allocator stashes
@@ -2421,6 +2561,35 @@ void ivf_scan_col(hipStream_t s, const uint32_t* units, int32_t n_units,
     default: DG_SCAN_LAUNCH(16, 4); break;
   }
 #undef DG_SCAN_LAUNCH
+}
+
+void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
+                   const int64_t* csr_offsets, const int32_t* chunk_off,
+                   const int64_t* chunk_base, const float* tvec,
+                   const float* vnorms, const float* queries, int32_t d,
+                   const int32_t* inv_offsets, const int32_t* inv_q,
+                   const int32_t* inv_rank, int32_t nprobe, int metric,
+                   const uint32_t* bitmap, int32_t chunk_rows, int32_t k,
+                   int32_t cpl_max, uint64_t* partial) {
+  if (!n_units) return;
+  // same tile ladder as the default ivf_scan_col pipeline
+#define DG_PIPE_LAUNCH(QTM)                                                 \
+  do {                                                                      \
+    size_t lds = (size_t)(QTM) * d * 4 + (QTM) * 8;                         \
+    hipLaunchKernelGGL((k_ivf_scan_pipe<(QTM), true, true>),                \
+                       dim3((uint32_t)n_units), dim3(256), lds, s, units,   \
+                       csr_offsets, chunk_off, chunk_base, tvec, vnorms,    \
+                       queries, d, inv_offsets, inv_q, inv_rank, nullptr,   \
+                       nullptr, nprobe, metric, bitmap, chunk_rows,         \
+                       partial, k, cpl_max);                                \
+  } while (0)
+  if (d <= 2304)
+    DG_PIPE_LAUNCH(16);
+  else if (d <= 4608)
+    DG_PIPE_LAUNCH(8);
+  else
+    DG_PIPE_LAUNCH(4);
+#undef DG_PIPE_LAUNCH
 }
 
 void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,

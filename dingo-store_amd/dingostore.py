@@ -328,6 +328,14 @@ class Index:
         idx.m = 0
         return idx
 
+    def last_scan_fused(self):
+        """True if the last IVF search that ran its kernels kept the
+        per-wave top-k inside the scan (see dg_last_scan_fused)."""
+        l = lib()
+        l.dg_last_scan_fused.argtypes = [C.c_void_p]
+        l.dg_last_scan_fused.restype = C.c_int
+        return bool(l.dg_last_scan_fused(self.h))
+
     def stats(self):
         s = _Stats()
         _check(lib().dg_stats(self.h, C.byref(s)), "dg_stats")

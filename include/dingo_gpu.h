@@ -248,6 +248,10 @@ void dg_unlock_write(dg_index* idx);
 /* ---- introspection ---- */
 dg_status dg_stats(dg_index* idx, dg_stats_out* out);
 void dg_last_error(char* buf, int64_t len);
+/* 1 if the last IVF search that ran its kernels (not a graph replay) kept
+ * the per-wave top-k inside the scan, 0 if it stored every candidate
+ * (range search, IVF-PQ, large k, oversized slots, DG_SCAN_FUSED=0). */
+int dg_last_scan_fused(dg_index* idx);
 int dg_device_count(void);
 /* Library self-identification: returns a static string with build arch. */
 const char* dg_build_info(void);
