@@ -202,6 +202,24 @@ static dg_status download_rows_strip(dg_index* ix, float* dst,
 // per-index exclusive-scan scratch (was a process-wide static
 // racing across indexes/devices).  n = scan length; scratch holds one i64
 // per 256-element block.
+// longest exclusive scan the 1024 block sums cover (n + 1 outputs); the
+// binary entry points validate nlist and nq against it
+static constexpr int32_t kMaxScanLen = 1023 * 256 - 1;  // 261887
+
+// Float and binary indexes have separate entry points (float32 rows against
+// packed uint8 rows); calling one family on the other kind is DG_EINVAL.
+static bool entry_matches(const dg_index* ix, bool binary_entry,
+                          const char* fn) {
+  if (ix->is_bin == binary_entry) return true;
+  if (binary_entry)
+    dg_set_error("%s called on a float index (kind %d): use the float32 "
+                 "entry point", fn, ix->desc.kind);
+  else
+    dg_set_error("%s called on a binary index (kind %d): use the "
+                 "dg_*_binary entry point", fn, ix->desc.kind);
+  return false;
+}
+
 static int64_t* scan_scratch(dg_index* ix, dg_status* st) {
   // k_scan_add_offsets holds the block sums in a 1024-entry LDS array, so
   // scan length is capped at 1023*256 elements (nlist and nq are far below)
@@ -263,13 +281,34 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
     return DG_EINVAL;
   }
   dg_index_desc desc = *dp;
-  if (desc.d <= 0 || desc.d > 8192) {
+  const bool is_bin = dg_kind_is_binary(desc.kind);
+  if (is_bin) {
+    // binary kinds: d in bits, whole bytes (faiss IndexBinary code_size)
+    if (desc.d < 8 || desc.d > 32768 || desc.d % 8 != 0) {
+      dg_set_error("binary dimension %d unsupported (need d %% 8 == 0 and "
+                   "8 <= d <= 32768 bits)", desc.d);
+      return DG_EINVAL;
+    }
+    if (desc.metric != DG_METRIC_HAMMING) {
+      dg_set_error("binary index needs the Hamming metric (got metric %d)",
+                   desc.metric);
+      return DG_EINVAL;
+    }
+    if (desc.kind == DG_INDEX_BINARY_IVF_FLAT) {
+      // kCreateBinaryIvfFlatParamNcentroids, constant.h:180
+      if (desc.nlist <= 0) desc.nlist = 2048;
+      if (desc.nlist > kMaxScanLen) {  // see scan_scratch
+        dg_set_error("nlist %d > %d unsupported", desc.nlist, kMaxScanLen);
+        return DG_EINVAL;
+      }
+    }
+  } else if (desc.d <= 0 || desc.d > 8192) {
     dg_set_error("dimension %d unsupported (need 0 < d <= 8192)", desc.d);
     return desc.d <= 0 ? DG_EINVAL : DG_ENOT_SUPPORT;
   }
   const int32_t d_user = desc.d;
-  desc.d = (desc.d + 3) & ~3;  // internal pad (see dg_internal.h)
-  if (desc.metric < 0 || desc.metric > 2) {
+  if (!is_bin) desc.d = (desc.d + 3) & ~3;  // internal pad (dg_internal.h)
+  if (!is_bin && (desc.metric < 0 || desc.metric > 2)) {
     dg_set_error("bad metric %d", desc.metric);
     return DG_EINVAL;
   }
@@ -288,11 +327,11 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
     }
   }
   if (desc.kind != DG_INDEX_FLAT && desc.kind != DG_INDEX_IVF_FLAT &&
-      desc.kind != DG_INDEX_IVF_PQ) {
+      desc.kind != DG_INDEX_IVF_PQ && !is_bin) {
     dg_set_error("bad kind %d", desc.kind);
     return DG_EINVAL;
   }
-  if (desc.kind != DG_INDEX_FLAT && desc.nlist <= 0)
+  if (!dg_kind_is_flat(desc.kind) && desc.nlist <= 0)
     desc.nlist = 2048;  // kCreateIvfFlatParamNcentroids, constant.h:177
   if (dg_device_count() == 0) {
     dg_set_error("no HIP device (the GPU path has no CPU fallback)");
@@ -301,6 +340,8 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   dg_index* ix = new dg_index();
   ix->desc = desc;
   ix->d_user = d_user;
+  ix->is_bin = is_bin;
+  ix->b_wp = is_bin ? (d_user + 31) / 32 : 0;
   ix->device = desc.device >= 0 ? desc.device : 0;
   DeviceGuard g(ix->device);
   if (hipStreamCreate(&ix->stream) != hipSuccess ||
@@ -313,7 +354,7 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   for (auto& e : ix->ev) (void)hipEventCreate(&e);
   ix->events_ready = true;
   (void)hipHostMalloc((void**)&ix->h_pinned, 64);
-  if (desc.kind == DG_INDEX_FLAT) ix->trained = true;
+  if (dg_kind_is_flat(desc.kind)) ix->trained = true;
   if (desc.reserve > 0) {  // capacity hint: avoids grow-copies during add
     // PQ never stores raw vectors (codes only); others reserve the vector
     // store up front
@@ -325,7 +366,10 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
     if (ok && desc.kind == DG_INDEX_IVF_PQ)
       ok = dbuf_reserve(ix->d_codes, (size_t)desc.reserve * desc.pq_m,
                         ix->stream, false) == DG_OK;
-    if (ok && desc.kind != DG_INDEX_IVF_PQ)
+    if (ok && is_bin)
+      ok = dbuf_reserve(ix->d_codes, (size_t)desc.reserve * ix->b_wp * 4,
+                        ix->stream, false) == DG_OK;
+    if (ok && desc.kind != DG_INDEX_IVF_PQ && !is_bin)
       ok = dbuf_reserve(ix->d_vectors, (size_t)desc.reserve * desc.d * 4,
                         ix->stream, false) == DG_OK;
     if (!ok) {
@@ -364,6 +408,7 @@ extern "C" void dg_index_destroy(dg_index* ix) {
 extern "C" dg_status dg_set_centroids(dg_index* ix, int32_t nlist,
                                       const float* centroids) {
   if (!ix || !centroids) return DG_EINVAL;
+  if (!entry_matches(ix, false, "dg_set_centroids")) return DG_EINVAL;
   if (ix->desc.kind == DG_INDEX_FLAT) {
     dg_set_error("set_centroids on non-IVF index");
     return DG_EINVAL;
@@ -395,6 +440,7 @@ extern "C" dg_status dg_set_centroids(dg_index* ix, int32_t nlist,
 
 extern "C" dg_status dg_get_centroids(dg_index* ix, float* out) {
   if (!ix || !out) return DG_EINVAL;
+  if (!entry_matches(ix, false, "dg_get_centroids")) return DG_EINVAL;
   if (!ix->trained || ix->desc.kind == DG_INDEX_FLAT) {
     dg_set_error("not trained");
     return DG_ENOT_TRAINED;
@@ -403,6 +449,70 @@ extern "C" dg_status dg_get_centroids(dg_index* ix, float* out) {
   DeviceGuard g(ix->device);
   return download_rows_strip(ix, out, (const float*)ix->d_centroids.p,
                              ix->desc.nlist);
+}
+
+// ---------------- binary rows: upload / centroids ----------------
+// upload n rows of d/8 bytes (host or device source) into word rows of
+// b_wp u32, zero-filling the pad bytes (zero pads XOR to zero)
+static dg_status upload_bits_padded(dg_index* ix, uint32_t* dst,
+                                    const uint8_t* src, int64_t n,
+                                    bool src_on_device) {
+  const size_t rb = (size_t)ix->d_user / 8, wb = (size_t)ix->b_wp * 4;
+  const hipMemcpyKind kind =
+      src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (rb == wb) {
+    DG_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n * rb, kind, ix->stream));
+    return DG_OK;
+  }
+  DG_HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)n * wb, ix->stream));
+  DG_HIP_CHECK(hipMemcpy2DAsync(dst, wb, src, rb, rb, (size_t)n, kind,
+                                ix->stream));
+  return DG_OK;
+}
+
+extern "C" dg_status dg_set_centroids_binary(dg_index* ix, int32_t nlist,
+                                             const uint8_t* centroids) {
+  if (!ix || !centroids) return DG_EINVAL;
+  if (!entry_matches(ix, true, "dg_set_centroids_binary")) return DG_EINVAL;
+  if (ix->desc.kind != DG_INDEX_BINARY_IVF_FLAT) {
+    dg_set_error("set_centroids on non-IVF index");
+    return DG_EINVAL;
+  }
+  if (nlist <= 0 || nlist > ix->desc.nlist) {
+    dg_set_error("nlist %d out of range (create nlist %d)", nlist,
+                 ix->desc.nlist);
+    return DG_EINVAL;
+  }
+  std::unique_lock lk(ix->rw);
+  DeviceGuard g(ix->device);
+  ix->desc.nlist = nlist;
+  dg_status st = dbuf_reserve(ix->d_centroids, (size_t)nlist * ix->b_wp * 4,
+                              ix->stream, false);
+  if (st != DG_OK) return st;
+  st = upload_bits_padded(ix, (uint32_t*)ix->d_centroids.p, centroids, nlist,
+                          false);
+  if (st != DG_OK) return st;
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  ix->trained = true;
+  ix->csr_valid = false;
+  ix->index_gen++;
+  return DG_OK;
+}
+
+extern "C" dg_status dg_get_centroids_binary(dg_index* ix, uint8_t* out) {
+  if (!ix || !out) return DG_EINVAL;
+  if (!entry_matches(ix, true, "dg_get_centroids_binary")) return DG_EINVAL;
+  if (!ix->trained || ix->desc.kind != DG_INDEX_BINARY_IVF_FLAT) {
+    dg_set_error("not trained");
+    return DG_ENOT_TRAINED;
+  }
+  std::shared_lock lk(ix->rw);
+  DeviceGuard g(ix->device);
+  const size_t rb = (size_t)ix->d_user / 8;
+  DG_HIP_CHECK(hipMemcpy2D(out, rb, ix->d_centroids.p, (size_t)ix->b_wp * 4,
+                           rb, (size_t)ix->desc.nlist,
+                           hipMemcpyDeviceToHost));
+  return DG_OK;
 }
 
 // ---------------- train (GPU k-means; faiss Clustering semantics
@@ -630,6 +740,7 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
     dg_set_error("bad train args");
     return DG_EINVAL;
   }
+  if (!entry_matches(ix, false, "dg_train")) return DG_EINVAL;
   if (ix->desc.kind == DG_INDEX_FLAT) return DG_OK;  // Flat needs no train
   std::unique_lock lk(ix->rw);
   if (ix->trained) return DG_OK;  // no-op, ivf_flat.cc:669-671
@@ -722,6 +833,94 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
   return st;
 }
 
+// Binary train: IndexBinaryIVF::train as the reference drives it
+// (vector_index_ivf_flat.cc:578-635) — bits unpacked to +-1 floats, the
+// same L2 k-means as the float indexes, centroids binarised with > 0.
+// The 256*nlist subsample kmeans_device would take is drawn here on the
+// packed host rows (same permutation), so only the sample is unpacked.
+extern "C" dg_status dg_train_binary(dg_index* ix, int64_t n,
+                                     const uint8_t* x) {
+  if (!ix || !x || n <= 0) {
+    dg_set_error("bad train args");
+    return DG_EINVAL;
+  }
+  if (!entry_matches(ix, true, "dg_train_binary")) return DG_EINVAL;
+  if (ix->desc.kind == DG_INDEX_BINARY_FLAT) return DG_OK;
+  std::unique_lock lk(ix->rw);
+  if (ix->trained) return DG_OK;  // no-op, ivf_flat.cc:585-588
+  DeviceGuard g(ix->device);
+  if (n < ix->desc.nlist) ix->desc.nlist = 1;  // degrade, ivf_flat.cc:593-597
+  const int32_t nlist = ix->desc.nlist;
+  const int32_t d = ix->d_user, wp = ix->b_wp;
+  const size_t rb = (size_t)d / 8;
+  const uint32_t seed = 1234;
+  const int64_t maxp = (int64_t)256 * nlist;
+  std::vector<uint8_t> sample;
+  const uint8_t* src = x;
+  int64_t nt = n;
+  if (n > maxp) {
+    std::vector<int64_t> perm;
+    rand_perm(perm, n, seed);
+    sample.resize((size_t)maxp * rb);
+    for (int64_t i = 0; i < maxp; i++)
+      memcpy(&sample[(size_t)i * rb], x + (size_t)perm[i] * rb, rb);
+    src = sample.data();
+    nt = maxp;
+  }
+  dg_dbuf d_bits{}, d_f{}, d_cf{};
+  DbufGuard g1(d_bits), g2(d_f), g3(d_cf);
+  dg_status st;
+  if ((st = dbuf_reserve(d_bits, (size_t)nt * wp * 4, ix->stream, false)) !=
+          DG_OK ||
+      (st = dbuf_reserve(d_f, (size_t)nt * d * 4, ix->stream, false)) !=
+          DG_OK ||
+      (st = dbuf_reserve(d_cf, (size_t)nlist * d * 4, ix->stream, false)) !=
+          DG_OK ||
+      (st = dbuf_reserve(ix->d_centroids, (size_t)nlist * wp * 4, ix->stream,
+                         false)) != DG_OK)
+    return st;
+  if ((st = upload_bits_padded(ix, (uint32_t*)d_bits.p, src, nt, false)) !=
+      DG_OK)
+    return st;
+  dgk::bits_to_pm1(ix->stream, (const uint32_t*)d_bits.p, nt, d, wp,
+                   (float*)d_f.p);
+  st = kmeans_device(ix, (const float*)d_f.p, nt, d, nlist, DG_METRIC_L2,
+                     seed, (float*)d_cf.p);
+  if (st != DG_OK) return st;
+  dgk::binarise(ix->stream, (const float*)d_cf.p, nlist, d, wp,
+                (uint32_t*)ix->d_centroids.p);
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  ix->trained = true;
+  ix->csr_valid = false;
+  ix->index_gen++;
+  return DG_OK;
+}
+
+// add-time assignment of packed rows: nearest centroid by Hamming distance,
+// ties toward the smaller list
+static dg_status assign_bits(dg_index* ix, const uint32_t* d_x, int64_t n,
+                             int32_t* d_assign) {
+  const int32_t nlist = ix->desc.nlist, wp = ix->b_wp;
+  if (nlist == 1) {
+    dgk::iota_i32(ix->stream, d_assign, n, 0);
+    return DG_OK;
+  }
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>(n, (int64_t)(512ull << 20) / ((size_t)nlist * 4)));
+  dg_status st =
+      dbuf_reserve(ix->ws_dots, (size_t)chunk * nlist * 4, ix->stream, false);
+  if (st != DG_OK) return st;
+  for (int64_t s0 = 0; s0 < n; s0 += chunk) {
+    const int64_t c = std::min(chunk, n - s0);
+    dgk::hamming_dists(ix->stream, d_x + (size_t)s0 * wp, c,
+                       (const uint32_t*)ix->d_centroids.p, nlist, wp,
+                       (float*)ix->ws_dots.p, nlist);
+    dgk::argmin_score(ix->stream, (const float*)ix->ws_dots.p, c, nlist,
+                      d_assign + s0);
+  }
+  return DG_OK;
+}
+
 // PQ encode: residual -> per-subspace argmin against codebooks.
 // d_x must already be cosine-normalized when applicable.
 static dg_status pq_encode(dg_index* ix, const float* d_x, int64_t n,
@@ -774,11 +973,14 @@ static dg_status pq_encode(dg_index* ix, const float* d_x, int64_t n,
 
 // ---------------- add / remove ----------------
 static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
-                          const float* x, bool x_on_device) {
-  if (!ix || !ids || !x || n <= 0) {
+                          const void* xv, bool x_on_device,
+                          bool binary_entry, const char* fn) {
+  if (!ix || !ids || !xv || n <= 0) {
     dg_set_error("bad add args");
     return DG_EINVAL;
   }
+  if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
+  const float* x = (const float*)xv;  // float kinds
   std::unique_lock lk(ix->rw);
   if (!ix->trained) {
     dg_set_error("IVF index not trained (EVECTOR_NOT_TRAIN)");
@@ -814,7 +1016,8 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
     return DG_ENOT_TRAINED;
   }
   dg_status st = DG_OK;
-  if (!is_pq)  // PQ never keeps raw vectors (cfg D: 100M x 768 > HBM)
+  if (!is_pq && !ix->is_bin)  // PQ never keeps raw vectors (cfg D: 100M x
+                              // 768 > HBM); binary keeps packed words
     st = dbuf_reserve(ix->d_vectors, (size_t)(n0 + n) * d * 4, ix->stream,
                       true);
   if (st == DG_OK)
@@ -824,7 +1027,31 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   if (st == DG_OK && is_pq)
     st = dbuf_reserve(ix->d_codes, (size_t)(n0 + n) * ix->desc.pq_m,
                       ix->stream, true);
+  if (st == DG_OK && ix->is_bin)
+    st = dbuf_reserve(ix->d_codes, (size_t)(n0 + n) * ix->b_wp * 4,
+                      ix->stream, true);
   if (st != DG_OK) return st;
+  if (ix->is_bin) {
+    uint32_t* wdst = (uint32_t*)ix->d_codes.p + (size_t)n0 * ix->b_wp;
+    st = upload_bits_padded(ix, wdst, (const uint8_t*)xv, n, x_on_device);
+    if (st != DG_OK) return st;
+    DG_HIP_CHECK(hipMemcpyAsync((int64_t*)ix->d_ids.p + n0, ids,
+                                (size_t)n * 8, hipMemcpyHostToDevice,
+                                ix->stream));
+    if (ix->desc.kind == DG_INDEX_BINARY_FLAT) {  // one implicit list; Flat
+      // has no centroids, whatever nlist its descriptor carried
+      dgk::iota_i32(ix->stream, (int32_t*)ix->d_assign.p + n0, n, 0);
+    } else {
+      st = assign_bits(ix, wdst, n, (int32_t*)ix->d_assign.p + n0);
+      if (st != DG_OK) return st;
+    }
+    DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+    for (int64_t i = 0; i < n; i++) ix->id_count.emplace(ids[i], 1);
+    ix->ntotal += n;
+    ix->csr_valid = false;
+    ix->index_gen++;
+    return DG_OK;
+  }
   dg_dbuf staging{};
   float* dst;
   if (is_pq) {  // stage the incoming chunk (never mutate the caller's)
@@ -867,7 +1094,12 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
 
 extern "C" dg_status dg_add(dg_index* ix, int64_t n, const int64_t* ids,
                             const float* x) {
-  return add_impl(ix, n, ids, x, false);
+  return add_impl(ix, n, ids, x, false, false, "dg_add");
+}
+
+extern "C" dg_status dg_add_binary(dg_index* ix, int64_t n,
+                                   const int64_t* ids, const uint8_t* x) {
+  return add_impl(ix, n, ids, x, false, true, "dg_add_binary");
 }
 
 // faiss-file loader ingestion (dg_internal.h): rows arrive with their
@@ -921,7 +1153,7 @@ dg_status dg_ingest_rows(dg_index* ix, int64_t n, const int64_t* ids,
 
 extern "C" dg_status dg_add_device(dg_index* ix, int64_t n,
                                    const int64_t* ids, const float* d_x) {
-  return add_impl(ix, n, ids, d_x, true);
+  return add_impl(ix, n, ids, d_x, true, false, "dg_add_device");
 }
 
 extern "C" dg_status dg_export_assign(dg_index* ix, int32_t* out) {
@@ -971,9 +1203,11 @@ extern "C" dg_status dg_remove(dg_index* ix, int64_t n, const int64_t* ids) {
   return DG_OK;
 }
 
-extern "C" dg_status dg_upsert(dg_index* ix, int64_t n, const int64_t* ids,
-                               const float* x) {
+static dg_status upsert_impl(dg_index* ix, int64_t n, const int64_t* ids,
+                             const void* x, bool binary_entry,
+                             const char* fn) {
   if (!ix || !ids || !x || n <= 0) return DG_EINVAL;
+  if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
   std::vector<int64_t> existing;
   {
     std::shared_lock lk(ix->rw);
@@ -984,7 +1218,17 @@ extern "C" dg_status dg_upsert(dg_index* ix, int64_t n, const int64_t* ids,
     dg_status st = dg_remove(ix, existing.size(), existing.data());
     if (st != DG_OK) return st;
   }
-  return dg_add(ix, n, ids, x);
+  return add_impl(ix, n, ids, x, false, binary_entry, fn);
+}
+
+extern "C" dg_status dg_upsert(dg_index* ix, int64_t n, const int64_t* ids,
+                               const float* x) {
+  return upsert_impl(ix, n, ids, x, false, "dg_upsert");
+}
+
+extern "C" dg_status dg_upsert_binary(dg_index* ix, int64_t n,
+                                      const int64_t* ids, const uint8_t* x) {
+  return upsert_impl(ix, n, ids, x, true, "dg_upsert_binary");
 }
 
 extern "C" dg_status dg_set_list_mask(dg_index* ix, const uint8_t* mask) {
@@ -995,7 +1239,8 @@ extern "C" dg_status dg_set_list_mask(dg_index* ix, const uint8_t* mask) {
     ix->has_mask = false;
     return DG_OK;
   }
-  if (ix->desc.kind != DG_INDEX_IVF_FLAT) {
+  if (ix->desc.kind != DG_INDEX_IVF_FLAT &&
+      ix->desc.kind != DG_INDEX_BINARY_IVF_FLAT) {
     dg_set_error("list mask on non-IVF index");
     return DG_EINVAL;
   }
@@ -1013,14 +1258,20 @@ extern "C" dg_status dg_set_list_mask(dg_index* ix, const uint8_t* mask) {
 static dg_status finalize_csr(dg_index* ix) {
   const bool is_ivf = ix->desc.kind == DG_INDEX_IVF_FLAT;
   const bool is_pq = ix->desc.kind == DG_INDEX_IVF_PQ;
-  const int32_t nlist = ix->desc.kind == DG_INDEX_FLAT ? 1 : ix->desc.nlist;
-  const int32_t d = ix->desc.d;
+  const bool is_bin = ix->is_bin;
+  const bool bin_ivf = ix->desc.kind == DG_INDEX_BINARY_IVF_FLAT;
+  const int32_t nlist = dg_kind_is_flat(ix->desc.kind) ? 1 : ix->desc.nlist;
+  // 4-byte columns per row: float dims, or packed words for the binary kinds
+  const int32_t d = is_bin ? ix->b_wp : ix->desc.d;
   const int64_t n = ix->ntotal;
   const int32_t CR = dg_index::kChunkRows;
   dg_status st;
-  // row-major target: persistent for FLAT (rocBLAS dots), temporary for IVF
+  // row-major target: persistent for FLAT (rocBLAS dots) and binary Flat
+  // (k_hamming_dists), temporary for the IVF kinds that scan chunks
   dg_dbuf rm_tmp{};
-  dg_dbuf& rowmajor = is_ivf ? rm_tmp : ix->d_csr_vectors;
+  dg_dbuf& rowmajor = (is_ivf || bin_ivf) ? rm_tmp
+                      : is_bin            ? ix->d_csr_codes
+                                          : ix->d_csr_vectors;
   if ((st = dbuf_reserve(ix->d_csr_offsets, ((size_t)nlist + 1) * 8,
                          ix->stream, false)) != DG_OK ||
       (st = dbuf_reserve(ix->d_csr_ids, (size_t)n * 8, ix->stream, false)) !=
@@ -1032,8 +1283,9 @@ static dg_status finalize_csr(dg_index* ix) {
   if (!is_pq &&
       ((st = dbuf_reserve(rowmajor, (size_t)n * d * 4, ix->stream, false)) !=
            DG_OK ||
-       (st = dbuf_reserve(ix->d_csr_vnorms, (size_t)n * 4, ix->stream,
-                          false)) != DG_OK)) {
+       (!is_bin &&
+        (st = dbuf_reserve(ix->d_csr_vnorms, (size_t)n * 4, ix->stream,
+                           false)) != DG_OK))) {
     dbuf_free(rm_tmp);
     return st;
   }
@@ -1060,6 +1312,9 @@ static dg_status finalize_csr(dg_index* ix) {
     if (is_pq) {
       dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_codes.p, d_perm, n,
                         ix->desc.pq_m, (uint8_t*)ix->d_csr_codes.p);
+    } else if (is_bin) {  // word rows move as b_wp * 4 byte codes
+      dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_codes.p, d_perm, n,
+                        d * 4, (uint8_t*)rowmajor.p);
     } else {
       dgk::gather_rows(ix->stream, (const float*)ix->d_vectors.p, d_perm, n,
                        d, (float*)rowmajor.p);
@@ -1077,7 +1332,7 @@ static dg_status finalize_csr(dg_index* ix) {
                               ix->stream));
   DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
 
-  if ((is_ivf || is_pq) && n > 0) {
+  if ((is_ivf || is_pq || bin_ivf) && n > 0) {
     // candidate-buffer upper bounds: prefix of list lens sorted descending
     // (lets searches size ws_cand without a device readback)
     std::vector<int64_t> lens(nlist);
@@ -1119,6 +1374,13 @@ static dg_status finalize_csr(dg_index* ix) {
       dbuf_free(rm_tmp);
       return st;
     }
+    if (bin_ivf &&  // word-major chunks; the binary scan reads no slack
+        (st = dbuf_reserve(ix->d_csr_t,
+                           (size_t)std::max<int64_t>(t_elems, 1) * 4,
+                           ix->stream, false)) != DG_OK) {
+      dbuf_free(rm_tmp);
+      return st;
+    }
     if (is_ivf &&
         // slack past the last chunk: the glds scan's tail quarters issue
         // padded reads (d columns) and the asm-pipelined scan runs up to 15
@@ -1150,6 +1412,11 @@ static dg_status finalize_csr(dg_index* ix) {
                             d_offsets, d_chunk_off, d_chunk_base,
                             (const float*)rowmajor.p, d, CR,
                             (float*)ix->d_csr_t.p);
+    if (bin_ivf)
+      dgk::transpose_chunks_u32(ix->stream, d_all_units, ix->total_chunks,
+                                d_offsets, d_chunk_off, d_chunk_base,
+                                (const uint32_t*)rowmajor.p, d, CR,
+                                (uint32_t*)ix->d_csr_t.p);
     DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
   }
   dbuf_free(rm_tmp);
@@ -1177,12 +1444,24 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                              int32_t k, int32_t nprobe,
                              const dg_filter* filter, float* d_out_dist,
                              int64_t* d_out_ids, dg_range_req* rr = nullptr) {
-  const int32_t d = ix->desc.d;
+  // binary kinds: d_x is packed uint8 rows; queries, rows and centroids
+  // are b_wp u32 words, so d counts 4-byte columns in both families
+  const bool is_bin = ix->is_bin;
+  const int32_t d = is_bin ? ix->b_wp : ix->desc.d;
   const int metric = ix->desc.metric;
-  const bool is_ivf = ix->desc.kind != DG_INDEX_FLAT;
+  const int emit_metric = is_bin ? (int)DG_METRIC_L2 : metric;  // no flip
+  const bool is_ivf = !dg_kind_is_flat(ix->desc.kind);
   const bool is_pq = ix->desc.kind == DG_INDEX_IVF_PQ;
   const int32_t nlist = is_ivf ? ix->desc.nlist : 1;
   dg_status st = DG_OK;
+  // dots[rows x cols]: f32 GEMM, or popcount(x ^ y) for the binary kinds
+  auto dots = [&](const float* X, int64_t rows, const void* Y, int64_t cols,
+                  float* out) -> dg_status {
+    if (!is_bin) return sgemm_dots(ix, X, rows, (const float*)Y, cols, d, out);
+    dgk::hamming_dists(ix->stream, (const uint32_t*)X, rows,
+                       (const uint32_t*)Y, cols, d, out, cols);
+    return DG_OK;
+  };
 
   if (!ix->capturing) (void)hipEventRecord(ix->ev[0], ix->stream);
 
@@ -1193,7 +1472,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           DG_OK)
     return st;
   float* dq = (float*)ix->ws_queries.p;
-  st = upload_rows_padded(ix, dq, d_x, nq, true);
+  st = is_bin ? upload_bits_padded(ix, (uint32_t*)dq, (const uint8_t*)d_x,
+                                   nq, true)
+              : upload_rows_padded(ix, dq, d_x, nq, true);
   if (st != DG_OK) return st;
   if (metric == DG_METRIC_COSINE) dgk::normalize_rows(ix->stream, dq, nq, d);
   float* dqn = (float*)ix->ws_qnorms.p;
@@ -1381,7 +1662,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     int64_t* bt = (int64_t*)(final_tk + (size_t)nq * k);   // base/total
     if (!ix->capturing) (void)hipEventRecord(ix->ev[1], ix->stream);  // no coarse stage in Flat
     if (!ix->capturing) (void)hipEventRecord(ix->ev[2], ix->stream);
-    const int mode = metric == DG_METRIC_L2 ? 1 : 2;
+    const int mode = is_bin ? 0 : metric == DG_METRIC_L2 ? 1 : 2;
+    const float* flat_rows = is_bin ? (const float*)ix->d_csr_codes.p
+                                    : (const float*)ix->d_csr_vectors.p;
     if (rr) {
       // range search: count pass + compact pass (GEMM recomputed — range
       // is not the measured hot path)
@@ -1434,9 +1717,8 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     for (int64_t ci = 0; ci < nchunks; ci++) {
       int64_t c0 = ci * chunk_cols;
       int64_t cc = std::min(chunk_cols, N - c0);
-      st = sgemm_dots(ix, dq, nq,
-                      (const float*)ix->d_csr_vectors.p + (size_t)c0 * d, cc,
-                      d, (float*)ix->ws_dots.p);
+      st = dots(dq, nq, flat_rows + (size_t)c0 * d, cc,
+                (float*)ix->ws_dots.p);
       if (st != DG_OK) break;
       dgk::select_dense(ix->stream, (const float*)ix->ws_dots.p,
                         (const float*)ix->d_csr_vnorms.p + c0, nq, cc, cc,
@@ -1452,11 +1734,14 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
         result = final_tk;
       }
       dgk::emit_results(ix->stream, result, (const int64_t*)ix->d_csr_ids.p,
-                        dqn, nq, k, metric, metric == DG_METRIC_L2 ? 1 : 0,
-                        d_out_dist, d_out_ids);
+                        dqn, nq, k, emit_metric,
+                        metric == DG_METRIC_L2 ? 1 : 0, d_out_dist,
+                        d_out_ids);
     }
     if (!ix->capturing) (void)hipEventRecord(ix->ev[4], ix->stream);
-    ix->times.last_scan_bytes_alg = (int64_t)ix->ntotal * (d * 4 + 4);
+    ix->times.last_scan_bytes_alg =
+        is_bin ? (int64_t)ix->ntotal * (ix->d_user / 8)
+               : (int64_t)ix->ntotal * (d * 4 + 4);
   } else {
     // ---------- IVF ----------
     // nprobe default + clamp (ivf_flat.cc:208-214, :234; default 80 =
@@ -1496,11 +1781,11 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
         dg_set_error("nprobe %d > 2048 (and < nlist) unsupported", np);
         return DG_ENOT_SUPPORT;
       }
-      st = sgemm_dots(ix, dq, nq, (const float*)ix->d_centroids.p, nlist, d,
-                      (float*)ix->ws_dots.p);
+      st = dots(dq, nq, ix->d_centroids.p, nlist, (float*)ix->ws_dots.p);
       if (st != DG_OK) {
         return st;
       }
+      const int cmode = is_bin ? 0 : metric == DG_METRIC_L2 ? 1 : 2;
       // segmented coarse top-np: one block per (query, <=8k-col segment),
       // merged with select_u64 (one block per query); at nlist <= 8192
       // this is the single-launch path of round 1
@@ -1517,8 +1802,8 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
         int64_t* bt_c = (int64_t*)(seg_slab + (size_t)nq * nseg_c * np);
         dgk::select_dense(ix->stream, (const float*)ix->ws_dots.p,
                           (const float*)ix->d_cnorms.p, nq, nlist, nlist,
-                          nseg_c, np, metric == DG_METRIC_L2 ? 1 : 2,
-                          nullptr, 0, seg_slab, (int64_t)nseg_c * np, 0);
+                          nseg_c, np, cmode, nullptr, 0, seg_slab,
+                          (int64_t)nseg_c * np, 0);
         dgk::fill_base_total(ix->stream, nq, (int64_t)nseg_c * np, bt_c,
                              bt_c + nq);
         dgk::select_u64(ix->stream, seg_slab, bt_c, bt_c + nq, nq, np,
@@ -1526,8 +1811,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
       } else {
         dgk::select_dense(ix->stream, (const float*)ix->ws_dots.p,
                           (const float*)ix->d_cnorms.p, nq, nlist, nlist, 1,
-                          np, metric == DG_METRIC_L2 ? 1 : 2, nullptr, 0,
-                          coarse_tk, np, 0);
+                          np, cmode, nullptr, 0, coarse_tk, np, 0);
       }
       dgk::probe_unpack(ix->stream, coarse_tk, nq, np, maskp, probes);
     }
@@ -1580,7 +1864,8 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     // (A/B switch, read per call like DG_NO_GRAPH).
     const int64_t partial_per_q =
         (int64_t)np * ix->cpl_max * (chunk_rows / 256) * k;
-    const bool fused = !is_pq && !rr && k <= dg_index::kScanFuseMaxK &&
+    const bool fused = !is_pq && !is_bin && !rr &&
+                       k <= dg_index::kScanFuseMaxK &&
                        nq * partial_per_q <= ub_cand && scan_fused_enabled();
     ix->last_scan_fused = fused;
     if (fused) {
@@ -1609,7 +1894,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     const int32_t total_units = ix->total_chunks;
     // algorithmic bytes (roofline) summed on device, read back async into
     // pinned memory; dg_stats synchronizes on ev[5]
-    const int64_t row_bytes = is_pq ? ix->desc.pq_m : (int64_t)(d * 4 + 4);
+    const int64_t row_bytes = is_pq    ? ix->desc.pq_m
+                              : is_bin ? (int64_t)(ix->d_user / 8)
+                                       : (int64_t)(d * 4 + 4);
     if (ix->h_pinned && !ix->capturing) {
       dg_dbuf& wsu = ix->ws_units;
       if ((st = dbuf_reserve(wsu, 8, ix->stream, false)) != DG_OK) {
@@ -1664,7 +1951,14 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           (const int64_t*)(mp + ((size_t)nlist + 1) * 4);
       const int32_t mean_probes =
           (int32_t)((nq * (int64_t)np) / std::max(1, nlist));
-      if (fused)
+      if (is_bin)
+        dgk::bivf_scan(ix->stream, units, total_units,
+                       (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
+                       d_chunk_base, (const uint32_t*)ix->d_csr_t.p,
+                       (const uint32_t*)dq, d, inv_offsets32, inv_q, inv_rank,
+                       qp_off, q_cand_base, np, d_bitmap, chunk_rows,
+                       (uint64_t*)ix->ws_cand.p);
+      else if (fused)
         dgk::ivf_scan_topk(ix->stream, units, total_units,
                            (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
                            d_chunk_base, (const float*)ix->d_csr_t.p,
@@ -1718,7 +2012,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                       q_total, nq, k, final_tk, k);
     }
     dgk::emit_results(ix->stream, final_tk, (const int64_t*)ix->d_csr_ids.p,
-                      dqn, nq, k, metric, metric == DG_METRIC_L2 ? 1 : 0,
+                      dqn, nq, k, emit_metric, metric == DG_METRIC_L2 ? 1 : 0,
                       d_out_dist, d_out_ids);
     if (!ix->capturing) (void)hipEventRecord(ix->ev[4], ix->stream);
   }
@@ -1729,12 +2023,21 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
 // NOTE: ivf_scan needs inv_offsets (int32) — computed as `cursors` would be
 // overwritten; see fix in search_core (we pass a dedicated buffer).
 
-extern "C" dg_status dg_search_device(dg_index* ix, int64_t nq,
-                                      const float* d_x, int32_t k,
-                                      int32_t nprobe, const dg_filter* filter,
-                                      float* d_out_dist, int64_t* d_out_ids) {
+// shared by the float and binary device-pointer entry points; d_x is
+// float32 rows or packed uint8 rows according to the index family
+static dg_status search_device_impl(dg_index* ix, int64_t nq,
+                                    const float* d_x, int32_t k,
+                                    int32_t nprobe, const dg_filter* filter,
+                                    float* d_out_dist, int64_t* d_out_ids,
+                                    bool binary_entry, const char* fn) {
   if (!ix || !d_x || !d_out_dist || !d_out_ids || nq <= 0) {
     dg_set_error("bad search args");
+    return DG_EINVAL;
+  }
+  if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
+  if (binary_entry && nq > kMaxScanLen) {
+    dg_set_error("nq %lld > %d per call unsupported", (long long)nq,
+                 kMaxScanLen);
     return DG_EINVAL;
   }
   if (k <= 0) return DG_OK;  // reference: topk <= 0 => OK no-op
@@ -1851,14 +2154,36 @@ extern "C" dg_status dg_search_device(dg_index* ix, int64_t nq,
   return search_core(ix, nq, d_x, k, nprobe, filter, d_out_dist, d_out_ids);
 }
 
-extern "C" dg_status dg_search(dg_index* ix, int64_t nq, const float* x,
-                               int32_t k, int32_t nprobe,
-                               const dg_filter* filter, float* out_dist,
-                               int64_t* out_ids) {
+extern "C" dg_status dg_search_device(dg_index* ix, int64_t nq,
+                                      const float* d_x, int32_t k,
+                                      int32_t nprobe, const dg_filter* filter,
+                                      float* d_out_dist, int64_t* d_out_ids) {
+  return search_device_impl(ix, nq, d_x, k, nprobe, filter, d_out_dist,
+                            d_out_ids, false, "dg_search_device");
+}
+
+extern "C" dg_status dg_search_binary_device(dg_index* ix, int64_t nq,
+                                             const uint8_t* d_x, int32_t k,
+                                             int32_t nprobe,
+                                             const dg_filter* filter,
+                                             float* d_out_dist,
+                                             int64_t* d_out_ids) {
+  return search_device_impl(ix, nq, (const float*)d_x, k, nprobe, filter,
+                            d_out_dist, d_out_ids, true,
+                            "dg_search_binary_device");
+}
+
+// host-pointer search of either family: x_row_bytes = caller's row stride
+static dg_status search_host_impl(dg_index* ix, int64_t nq, const void* x,
+                                  size_t x_row_bytes, int32_t k,
+                                  int32_t nprobe, const dg_filter* filter,
+                                  float* out_dist, int64_t* out_ids,
+                                  bool binary_entry, const char* fn) {
   if (!ix || !x || !out_dist || !out_ids || nq <= 0) {
     dg_set_error("bad search args");
     return DG_EINVAL;
   }
+  if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
   if (k <= 0) return DG_OK;
   DeviceGuard g(ix->device);
   // upload queries, run device path, download (per-thread staging keyed by
@@ -1866,17 +2191,18 @@ extern "C" dg_status dg_search(dg_index* ix, int64_t nq, const float* x,
   auto& tls = g_tls_staging.for_device(ix->device);
   dg_dbuf &t_in = tls.in, &t_dist = tls.dist, &t_ids = tls.ids;
   dg_status st;
-  if ((st = dbuf_reserve(t_in, (size_t)nq * ix->d_user * 4, ix->stream,
+  if ((st = dbuf_reserve(t_in, (size_t)nq * x_row_bytes, ix->stream,
                          false)) != DG_OK ||
       (st = dbuf_reserve(t_dist, (size_t)nq * k * 4, ix->stream, false)) !=
           DG_OK ||
       (st = dbuf_reserve(t_ids, (size_t)nq * k * 8, ix->stream, false)) !=
           DG_OK)
     return st;
-  DG_HIP_CHECK(hipMemcpyAsync(t_in.p, x, (size_t)nq * ix->d_user * 4,
+  DG_HIP_CHECK(hipMemcpyAsync(t_in.p, x, (size_t)nq * x_row_bytes,
                               hipMemcpyHostToDevice, ix->stream));
-  st = dg_search_device(ix, nq, (const float*)t_in.p, k, nprobe, filter,
-                        (float*)t_dist.p, (int64_t*)t_ids.p);
+  st = search_device_impl(ix, nq, (const float*)t_in.p, k, nprobe, filter,
+                          (float*)t_dist.p, (int64_t*)t_ids.p, binary_entry,
+                          fn);
   if (st != DG_OK) return st;
   DG_HIP_CHECK(hipMemcpyAsync(out_dist, t_dist.p, (size_t)nq * k * 4,
                               hipMemcpyDeviceToHost, ix->stream));
@@ -1884,6 +2210,24 @@ extern "C" dg_status dg_search(dg_index* ix, int64_t nq, const float* x,
                               hipMemcpyDeviceToHost, ix->stream));
   DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
   return DG_OK;
+}
+
+extern "C" dg_status dg_search(dg_index* ix, int64_t nq, const float* x,
+                               int32_t k, int32_t nprobe,
+                               const dg_filter* filter, float* out_dist,
+                               int64_t* out_ids) {
+  return search_host_impl(ix, nq, x, ix ? (size_t)ix->d_user * 4 : 0, k,
+                          nprobe, filter, out_dist, out_ids, false,
+                          "dg_search");
+}
+
+extern "C" dg_status dg_search_binary(dg_index* ix, int64_t nq,
+                                      const uint8_t* x, int32_t k,
+                                      int32_t nprobe, const dg_filter* filter,
+                                      float* out_dist, int64_t* out_ids) {
+  return search_host_impl(ix, nq, x, ix ? (size_t)ix->d_user / 8 : 0, k,
+                          nprobe, filter, out_dist, out_ids, true,
+                          "dg_search_binary");
 }
 
 extern "C" dg_status dg_sync(dg_index* ix) {
@@ -1905,6 +2249,10 @@ extern "C" dg_status dg_range_search(dg_index* ix, int64_t nq, const float* x,
   if (!ix || !x || !lims || !out_ids || !out_dists || nq <= 0) {
     dg_set_error("bad range search args");
     return DG_EINVAL;
+  }
+  if (ix->is_bin) {
+    dg_set_error("range search is not supported on binary indexes");
+    return DG_ENOT_SUPPORT;
   }
   DeviceGuard g(ix->device);
   if (!ix->trained || ix->ntotal == 0 ||
@@ -1946,6 +2294,10 @@ static const uint32_t kMagic = 0x44474931;  // "DGI1"
 
 extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   if (!ix || !path) return DG_EINVAL;
+  if (ix->is_bin) {
+    dg_set_error("save is not supported on binary indexes");
+    return DG_ENOT_SUPPORT;
+  }
   std::shared_lock lk(ix->rw);
   DeviceGuard g(ix->device);
   FILE* f = fopen(path, "wb");
@@ -2197,7 +2549,7 @@ extern "C" dg_status dg_stats(dg_index* ix, dg_stats_out* out) {
     // or overwrite the pinned alg-bytes scalar mid-read
     std::lock_guard sg(ix->search_mu);
     (void)hipEventSynchronize(ix->ev[4]);
-    if (ix->h_pinned && ix->desc.kind != DG_INDEX_FLAT) {
+    if (ix->h_pinned && !dg_kind_is_flat(ix->desc.kind)) {
       (void)hipEventSynchronize(ix->ev[5]);
       ix->times.last_scan_bytes_alg = *ix->h_pinned;
     }

@@ -66,6 +66,14 @@ struct dg_dbuf {
   size_t bytes = 0, cap = 0;
 };
 
+// kind helpers: the binary kinds share the Flat / IVF-Flat machinery
+static inline bool dg_kind_is_binary(int32_t kind) {
+  return kind == DG_INDEX_BINARY_FLAT || kind == DG_INDEX_BINARY_IVF_FLAT;
+}
+static inline bool dg_kind_is_flat(int32_t kind) {
+  return kind == DG_INDEX_FLAT || kind == DG_INDEX_BINARY_FLAT;
+}
+
 struct dg_stage_times {
   double coarse_ms = 0, scan_ms = 0, select_ms = 0, total_ms = 0;
   // cumulative since last reset (for bench averaging)
@@ -82,6 +90,13 @@ struct dg_index {
   // ABI.  Boundary copies are 2D (pitched) when d_user != desc.d.
   dg_index_desc desc;
   int32_t d_user = 0;
+  // Binary (Hamming) kinds: desc.d == d_user == dimension in BITS; rows,
+  // queries and centroids are held as b_wp = ceil(d/32) zero-padded u32
+  // words (DESIGN.md §Binary indexes).  The arrival store is d_codes
+  // ([ntotal x b_wp] words), the grouped row-major rows d_csr_codes (Flat
+  // only), the word-major chunks d_csr_t, the centroids d_centroids.
+  bool is_bin = false;
+  int32_t b_wp = 0;
   int device = 0;
   hipStream_t stream = nullptr;
   rocblas_handle blas = nullptr;
@@ -208,6 +223,32 @@ void gather_rows_by_index(hipStream_t s, const float* src, const int64_t* idx,
 void fill_base_total(hipStream_t s, int64_t nq, int64_t len, int64_t* base,
                      int64_t* total);
 void tombstone(hipStream_t s, const int64_t* pos, int64_t n, int64_t* ids);
+// binary (Hamming) indexes: packed u32 words, wp words per row
+// out[nq x cols] (row stride ld) = popcount(X[q] ^ Y[c]) as exact f32
+void hamming_dists(hipStream_t s, const uint32_t* X, int64_t nq,
+                   const uint32_t* Y, int64_t cols, int32_t wp, float* out,
+                   int64_t ld);
+// per-row argmin of a dense score matrix, ties toward the smaller column
+void argmin_score(hipStream_t s, const float* scores, int64_t n, int32_t cols,
+                  int32_t* out);
+void transpose_chunks_u32(hipStream_t s, const uint32_t* units,
+                          int32_t n_units, const int64_t* csr_offsets,
+                          const int32_t* chunk_off, const int64_t* chunk_base,
+                          const uint32_t* rowmajor, int32_t wp,
+                          int32_t chunk_rows, uint32_t* twords);
+// store-all candidate scan over word-major chunks (key = f32 distance)
+void bivf_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
+               const int64_t* csr_offsets, const int32_t* chunk_off,
+               const int64_t* chunk_base, const uint32_t* twords,
+               const uint32_t* queries, int32_t wp,
+               const int32_t* inv_offsets, const int32_t* inv_q,
+               const int32_t* inv_rank, const int64_t* qp_off,
+               const int64_t* q_cand_base, int32_t nprobe,
+               const uint32_t* bitmap, int32_t chunk_rows, uint64_t* cand);
+void bits_to_pm1(hipStream_t s, const uint32_t* x, int64_t n, int32_t d,
+                 int32_t wp, float* out);
+void binarise(hipStream_t s, const float* c, int64_t n, int32_t d, int32_t wp,
+              uint32_t* out);
 void row_norms(hipStream_t s, const float* x, int64_t n, int32_t d,
                float* out);
 void normalize_rows(hipStream_t s, float* x, int64_t n, int32_t d);

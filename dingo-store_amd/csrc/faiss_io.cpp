@@ -286,6 +286,10 @@ struct DeviceGuard {
 
 extern "C" dg_status dg_save_faiss(dg_index* ix, const char* path) {
   if (!ix || !path) return DG_EINVAL;
+  if (ix->is_bin) {
+    dg_set_error("faiss save is not supported on binary indexes");
+    return DG_ENOT_SUPPORT;
+  }
   std::shared_lock lk(ix->rw);
   DeviceGuard g{ix->device};
   const int32_t d = ix->d_user;  // containers speak the caller's dimension

@@ -2042,12 +2042,15 @@ __global__ void __launch_bounds__(256, 3) k_ivf_scan_col_hi(
 
 // tiled row-major -> column-major chunk transpose (finalize step).
 // One block per (list, chunk) unit over ALL chunks; LDS 64x65 tile.
+// T = float for the IVF-Flat columns, uint32_t for the packed words of the
+// binary indexes (d = words per row there).
+template <typename T>
 __global__ void k_transpose_chunks(
     const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
     const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
-    const float* __restrict__ rowmajor, int32_t d, int32_t chunk_rows,
-    float* __restrict__ tvec) {
-  __shared__ float tile[64][65];
+    const T* __restrict__ rowmajor, int32_t d, int32_t chunk_rows,
+    T* __restrict__ tvec) {
+  __shared__ T tile[64][65];
   const uint32_t list = units[2 * blockIdx.x];
   const uint32_t chunk = units[2 * blockIdx.x + 1];
   const int64_t list_start = csr_offsets[list];
@@ -2055,9 +2058,8 @@ __global__ void k_transpose_chunks(
   const int32_t nrows =
       (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
   const int32_t nrows_pad = (nrows + 3) & ~3;
-  const float* src =
-      rowmajor + (list_start + (int64_t)chunk * chunk_rows) * d;
-  float* dst = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+  const T* src = rowmajor + (list_start + (int64_t)chunk * chunk_rows) * d;
+  T* dst = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
 
   const int tx = threadIdx.x % 64;  // dim within tile on read, row on write
   const int ty = threadIdx.x / 64;  // 4 groups
@@ -2068,7 +2070,7 @@ __global__ void k_transpose_chunks(
         int32_t r = r0 + rr;
         tile[rr][tx] = (r < nrows && i0 + tx < d)
                            ? src[(size_t)r * d + i0 + tx]
-                           : 0.f;
+                           : T(0);
       }
       __syncthreads();
       for (int ii = ty; ii < 64; ii += 4) {
@@ -2304,6 +2306,206 @@ __global__ void k_scan_block_i64(const int64_t* in, int64_t n, int64_t* out,
   }
   if (i <= n) out[i] = lds[threadIdx.x] - v;
   if (threadIdx.x == 255) block_sums[blockIdx.x] = lds[255];
+}
+
+// ---------- binary (Hamming) indexes ----------
+// Rows, queries and centroids are bit vectors packed LSB-first into u32
+// words, zero-padded to wp = ceil(d/32) words (pads XOR to zero).  Distances
+// are exact integers; they travel as f32 (exact below 2^24, d <= 32768) so
+// the packed-u64 selection and k_emit are shared with the float indexes.
+
+// out[q][c] = popcount(X[q] ^ Y[c]); X [nq][wp], Y [cols][wp] row-major.
+// Block = 256 columns (one per thread) x kHamQ queries, words in tiles of
+// kHamW.  Y rows are staged through LDS (coalesced global reads, stride
+// kHamW+1 so the per-thread row walk is conflict-free); the query tile is
+// stored word-major so each thread reads it as wave-uniform b128 broadcasts.
+// Flat 1-D grid: tile_x + nx * tile_y (the row count of an add-time
+// assignment can exceed the 65535 limit of gridDim.y).
+static constexpr int kHamQ = 32;
+static constexpr int kHamW = 32;
+__global__ void __launch_bounds__(256) k_hamming_dists(
+    const uint32_t* __restrict__ X, int64_t nq, const uint32_t* __restrict__ Y,
+    int64_t cols, int32_t wp, uint32_t nx, float* __restrict__ out,
+    int64_t ld) {
+  __shared__ uint32_t ly[256 * (kHamW + 1)];
+  __shared__ __attribute__((aligned(16))) uint32_t lx[kHamW * kHamQ];
+  const int tid = threadIdx.x;
+  const int64_t c0 = (int64_t)(blockIdx.x % nx) * 256;
+  const int64_t q0 = (int64_t)(blockIdx.x / nx) * kHamQ;
+  int32_t acc[kHamQ];
+#pragma unroll
+  for (int j = 0; j < kHamQ; j++) acc[j] = 0;
+  for (int32_t w0 = 0; w0 < wp; w0 += kHamW) {
+    __syncthreads();
+    for (int i = tid; i < 256 * kHamW; i += 256) {
+      const int r = i / kHamW, w = i % kHamW;
+      ly[r * (kHamW + 1) + w] =
+          (c0 + r < cols && w0 + w < wp) ? Y[(size_t)(c0 + r) * wp + w0 + w]
+                                         : 0u;
+    }
+    for (int i = tid; i < kHamQ * kHamW; i += 256) {
+      const int q = i / kHamW, w = i % kHamW;
+      lx[w * kHamQ + q] =
+          (q0 + q < nq && w0 + w < wp) ? X[(size_t)(q0 + q) * wp + w0 + w]
+                                       : 0u;
+    }
+    __syncthreads();
+    const int32_t wn = min(kHamW, wp - w0);
+    for (int32_t w = 0; w < wn; w++) {
+      const uint32_t y = ly[tid * (kHamW + 1) + w];
+      const uint4* xv = (const uint4*)(lx + w * kHamQ);
+#pragma unroll
+      for (int j4 = 0; j4 < kHamQ / 4; j4++) {
+        const uint4 x = xv[j4];
+        acc[4 * j4 + 0] += __popc(y ^ x.x);
+        acc[4 * j4 + 1] += __popc(y ^ x.y);
+        acc[4 * j4 + 2] += __popc(y ^ x.z);
+        acc[4 * j4 + 3] += __popc(y ^ x.w);
+      }
+    }
+  }
+  if (c0 + tid >= cols) return;
+#pragma unroll
+  for (int j = 0; j < kHamQ; j++)
+    if (q0 + j < nq) out[(q0 + j) * ld + c0 + tid] = (float)acc[j];
+}
+
+// argmin over a dense score row, key = score as is; tie: smaller column
+__global__ void k_argmin_score(const float* __restrict__ scores, int64_t n,
+                               int32_t cols, int32_t* __restrict__ out) {
+  int64_t row = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+  int lane = threadIdx.x % WAVE;
+  if (row >= n) return;
+  const float* sr = scores + row * cols;
+  uint64_t best = kCandEmpty;
+  for (int l = lane; l < cols; l += WAVE)
+    best = min(best, pack_cand(sr[l], (uint32_t)l));
+  for (int off = 32; off; off >>= 1)
+    best = min(best, (uint64_t)__shfl_xor((long long)best, off, WAVE));
+  if (lane == 0) out[row] = (int32_t)(best & 0xffffffffu);
+}
+
+// THE binary scan: unit = (list, 1024-row chunk) in the word-major chunk
+// layout [wp][nrows_pad] u32.  Each thread owns 4 consecutive rows, so every
+// word step is one coalesced 16 B/lane load and there is no cross-lane
+// reduction.  The queries probing the list are staged in LDS QT at a time,
+// word-major, and read as wave-uniform b128 broadcasts; per (row, query)
+// pair a word costs one XOR and one accumulating popcount.  Writes the
+// store-all candidates exactly like k_ivfpq_scan (key = f32 distance).
+template <int QT>
+__global__ void __launch_bounds__(256) k_bivf_scan(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const uint32_t* __restrict__ twords, const uint32_t* __restrict__ queries,
+    int32_t wp, const int32_t* __restrict__ inv_offsets,
+    const int32_t* __restrict__ inv_q, const int32_t* __restrict__ inv_rank,
+    const int64_t* __restrict__ qp_off, const int64_t* __restrict__ q_cand_base,
+    int32_t nprobe, const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
+    uint64_t* __restrict__ cand) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_q[];  // [wp][QT]
+  __shared__ int64_t lds_cb[QT];
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int32_t iq0 = inv_offsets[list];
+  const int32_t nql = inv_offsets[list + 1] - iq0;
+  if (nql == 0) return;  // unprobed list (all-chunks launch)
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t pad = (nrows + 3) & ~3;
+  const int64_t row_start = list_start + (int64_t)chunk * chunk_rows;
+  const int tid = threadIdx.x;
+  const int32_t r0 = 4 * tid;
+  const bool active = r0 < pad;
+  const uint32_t* src =
+      twords + chunk_base[chunk_off[list] + (int32_t)chunk] + r0;
+  uint32_t pass = 0;
+  for (int i = 0; i < 4; i++) {
+    const int64_t rw = row_start + r0 + i;
+    if (r0 + i < nrows && (!bitmap || ((bitmap[rw >> 5] >> (rw & 31)) & 1)))
+      pass |= 1u << i;
+  }
+
+  for (int32_t t0 = 0; t0 < nql; t0 += QT) {
+    const int32_t qn = min(QT, nql - t0);
+    __syncthreads();  // the previous tile's readers are done
+    for (int32_t i = tid; i < QT * wp; i += blockDim.x) {
+      const int32_t j = i / wp, w = i % wp;
+      lds_q[w * QT + j] =
+          j < qn ? queries[(size_t)inv_q[iq0 + t0 + j] * wp + w] : 0u;
+    }
+    if (tid < QT) {
+      int64_t cb = 0;
+      if (tid < qn) {
+        const int32_t q = inv_q[iq0 + t0 + tid];
+        cb = q_cand_base[q] +
+             qp_off[(int64_t)q * nprobe + inv_rank[iq0 + t0 + tid]] -
+             list_start;
+      }
+      lds_cb[tid] = cb;
+    }
+    __syncthreads();
+    if (!active) continue;
+    int32_t acc[QT][4];
+#pragma unroll
+    for (int j = 0; j < QT; j++)
+      acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0;
+#pragma unroll 4
+    for (int32_t w = 0; w < wp; w++) {
+      const uint4 r = *(const uint4*)(src + (size_t)w * pad);
+      const uint4* qv = (const uint4*)(lds_q + w * QT);
+#pragma unroll
+      for (int j4 = 0; j4 < QT / 4; j4++) {
+        const uint4 qq = qv[j4];
+        const uint32_t qs[4] = {qq.x, qq.y, qq.z, qq.w};
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) {
+          acc[4 * j4 + jj][0] += __popc(r.x ^ qs[jj]);
+          acc[4 * j4 + jj][1] += __popc(r.y ^ qs[jj]);
+          acc[4 * j4 + jj][2] += __popc(r.z ^ qs[jj]);
+          acc[4 * j4 + jj][3] += __popc(r.w ^ qs[jj]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < QT; j++) {
+      if (j >= qn) break;
+      uint64_t* dst = cand + lds_cb[j] + row_start + r0;
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        if (r0 + i < nrows)
+          dst[i] = (pass >> i) & 1
+                       ? pack_cand((float)acc[j][i],
+                                   (uint32_t)(row_start + r0 + i))
+                       : kCandEmpty;
+    }
+  }
+}
+
+// bits -> +-1.0f rows (k-means input of the binary train); out [n][d]
+__global__ void k_bits_to_pm1(const uint32_t* __restrict__ x, int64_t n,
+                              int32_t d, int32_t wp, float* __restrict__ out) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * d) return;
+  const int64_t r = i / d;
+  const int32_t j = (int32_t)(i % d);
+  out[i] = ((x[(size_t)r * wp + (j >> 5)] >> (j & 31)) & 1) ? 1.0f : -1.0f;
+}
+
+// float centroids -> packed words, bit = (value > 0); out [n][wp]
+__global__ void k_binarise(const float* __restrict__ c, int64_t n, int32_t d,
+                           int32_t wp, uint32_t* __restrict__ out) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * wp) return;
+  const int64_t r = i / wp;
+  const int32_t w = (int32_t)(i % wp);
+  uint32_t bits = 0;
+  for (int b = 0; b < 32; b++) {
+    const int32_t j = w * 32 + b;
+    if (j < d && c[(size_t)r * d + j] > 0.f) bits |= 1u << b;
+  }
+  out[i] = bits;
 }
 
 // ---------- launchers ----------
@@ -2723,9 +2925,20 @@ void transpose_chunks(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int64_t* chunk_base, const float* rowmajor,
                       int32_t d, int32_t chunk_rows, float* tvec) {
   if (!n_units) return;
-  hipLaunchKernelGGL(k_transpose_chunks, dim3((uint32_t)n_units), dim3(256),
-                     0, s, units, csr_offsets, chunk_off, chunk_base,
-                     rowmajor, d, chunk_rows, tvec);
+  hipLaunchKernelGGL(k_transpose_chunks<float>, dim3((uint32_t)n_units),
+                     dim3(256), 0, s, units, csr_offsets, chunk_off,
+                     chunk_base, rowmajor, d, chunk_rows, tvec);
+}
+
+void transpose_chunks_u32(hipStream_t s, const uint32_t* units,
+                          int32_t n_units, const int64_t* csr_offsets,
+                          const int32_t* chunk_off, const int64_t* chunk_base,
+                          const uint32_t* rowmajor, int32_t wp,
+                          int32_t chunk_rows, uint32_t* twords) {
+  if (!n_units) return;
+  hipLaunchKernelGGL(k_transpose_chunks<uint32_t>, dim3((uint32_t)n_units),
+                     dim3(256), 0, s, units, csr_offsets, chunk_off,
+                     chunk_base, rowmajor, wp, chunk_rows, twords);
 }
 
 void dots_mfma(hipStream_t s, const float* X, int64_t M, const float* Y,
@@ -2808,6 +3021,51 @@ void fill_base_total(hipStream_t s, int64_t nq, int64_t len, int64_t* base,
 void tombstone(hipStream_t s, const int64_t* pos, int64_t n, int64_t* ids) {
   if (n) hipLaunchKernelGGL(k_tombstone, dim3(ceil_div(n, 256)), dim3(256), 0,
                             s, pos, n, ids);
+}
+
+// ---- binary (Hamming) indexes ----
+void hamming_dists(hipStream_t s, const uint32_t* X, int64_t nq,
+                   const uint32_t* Y, int64_t cols, int32_t wp, float* out,
+                   int64_t ld) {
+  if (!nq || !cols) return;
+  const int64_t nx = ceil_div(cols, 256), ny = ceil_div(nq, kHamQ);
+  hipLaunchKernelGGL(k_hamming_dists, dim3((uint32_t)(nx * ny)), dim3(256), 0,
+                     s, X, nq, Y, cols, wp, (uint32_t)nx, out, ld);
+}
+
+void argmin_score(hipStream_t s, const float* scores, int64_t n, int32_t cols,
+                  int32_t* out) {
+  if (n) hipLaunchKernelGGL(k_argmin_score, dim3(ceil_div(n, 4)),
+                            dim3(4 * WAVE), 0, s, scores, n, cols, out);
+}
+
+void bivf_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
+               const int64_t* csr_offsets, const int32_t* chunk_off,
+               const int64_t* chunk_base, const uint32_t* twords,
+               const uint32_t* queries, int32_t wp,
+               const int32_t* inv_offsets, const int32_t* inv_q,
+               const int32_t* inv_rank, const int64_t* qp_off,
+               const int64_t* q_cand_base, int32_t nprobe,
+               const uint32_t* bitmap, int32_t chunk_rows, uint64_t* cand) {
+  if (!n_units) return;
+  constexpr int QT = 8;  // 32 accumulators per thread; LDS = wp * 32 B
+  hipLaunchKernelGGL(k_bivf_scan<QT>, dim3((uint32_t)n_units), dim3(256),
+                     (size_t)wp * QT * 4, s, units, csr_offsets, chunk_off,
+                     chunk_base, twords, queries, wp, inv_offsets, inv_q,
+                     inv_rank, qp_off, q_cand_base, nprobe, bitmap,
+                     chunk_rows, cand);
+}
+
+void bits_to_pm1(hipStream_t s, const uint32_t* x, int64_t n, int32_t d,
+                 int32_t wp, float* out) {
+  if (n) hipLaunchKernelGGL(k_bits_to_pm1, dim3(ceil_div(n * d, 256)),
+                            dim3(256), 0, s, x, n, d, wp, out);
+}
+
+void binarise(hipStream_t s, const float* c, int64_t n, int32_t d, int32_t wp,
+              uint32_t* out) {
+  if (n) hipLaunchKernelGGL(k_binarise, dim3(ceil_div(n * wp, 256)), dim3(256),
+                            0, s, c, n, d, wp, out);
 }
 
 }  // namespace dgk

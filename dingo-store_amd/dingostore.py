@@ -15,8 +15,12 @@ _SO = os.path.join(_DIR, "libdingo_gpu.so")
 
 L2, IP, COSINE = 0, 1, 2
 FLAT, IVF_FLAT, IVF_PQ = 0, 1, 2
+# binary (Hamming) indexes: d is in bits, rows are np.uint8 [n, d // 8]
+BINARY_FLAT, BINARY_IVF_FLAT = 3, 4
+HAMMING = 3
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
+_u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 
 
@@ -87,6 +91,20 @@ def _load():
     lib.dg_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
     lib.dg_set_list_mask.argtypes = [C.c_void_p, C.c_void_p]
     lib.dg_mirror_selftest.restype = C.c_int
+    lib.dg_train_binary.argtypes = [C.c_void_p, C.c_int64, _u8p]
+    lib.dg_set_centroids_binary.argtypes = [C.c_void_p, C.c_int32, _u8p]
+    lib.dg_get_centroids_binary.argtypes = [C.c_void_p, _u8p]
+    lib.dg_add_binary.argtypes = [C.c_void_p, C.c_int64, _i64p, _u8p]
+    lib.dg_upsert_binary.argtypes = [C.c_void_p, C.c_int64, _i64p, _u8p]
+    lib.dg_search_binary.argtypes = [
+        C.c_void_p, C.c_int64, _u8p, C.c_int32, C.c_int32,
+        C.POINTER(_Filter), _f32p, _i64p,
+    ]
+    lib.dg_search_binary_device.argtypes = [
+        C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+        C.POINTER(_Filter), C.c_void_p, C.c_void_p,
+    ]
+    lib.dg_mirror_selftest_binary.restype = C.c_int
     return lib
 
 
@@ -108,7 +126,9 @@ def last_error():
 
 def _check(st, what):
     if st != 0:
-        raise DgError(f"{what} failed (status {st}): {last_error()}")
+        err = DgError(f"{what} failed (status {st}): {last_error()}")
+        err.status = st  # dg_status code, for callers that dispatch on it
+        raise err
 
 
 def build_info():
@@ -166,17 +186,39 @@ class Index:
         except Exception:
             pass
 
+    @property
+    def is_binary(self):
+        return self.kind in (BINARY_FLAT, BINARY_IVF_FLAT)
+
     def train(self, x):
+        if self.is_binary:
+            x = np.ascontiguousarray(x, np.uint8)
+            _check(lib().dg_train_binary(self.h, x.shape[0], x),
+                   "dg_train_binary")
+            self.nlist = self.stats()["nlist"]  # n < nlist degrades to 1
+            return
         x = np.ascontiguousarray(x, np.float32)
         _check(lib().dg_train(self.h, x.shape[0], x), "dg_train")
 
     def set_centroids(self, centroids):
+        if self.is_binary:
+            centroids = np.ascontiguousarray(centroids, np.uint8)
+            _check(lib().dg_set_centroids_binary(
+                self.h, centroids.shape[0], centroids),
+                "dg_set_centroids_binary")
+            self.nlist = centroids.shape[0]
+            return
         centroids = np.ascontiguousarray(centroids, np.float32)
         self.nlist = centroids.shape[0]
         _check(lib().dg_set_centroids(self.h, centroids.shape[0], centroids),
                "dg_set_centroids")
 
     def get_centroids(self):
+        if self.is_binary:
+            out = np.empty((self.stats()["nlist"], self.d // 8), np.uint8)
+            _check(lib().dg_get_centroids_binary(self.h, out),
+                   "dg_get_centroids_binary")
+            return out
         out = np.empty((self.nlist, self.d), np.float32)
         _check(lib().dg_get_centroids(self.h, out), "dg_get_centroids")
         return out
@@ -201,8 +243,13 @@ class Index:
         return out
 
     def add(self, ids, x):
-        x = np.ascontiguousarray(x, np.float32)
         ids = np.ascontiguousarray(ids, np.int64)
+        if self.is_binary:
+            x = np.ascontiguousarray(x, np.uint8)
+            _check(lib().dg_add_binary(self.h, x.shape[0], ids, x),
+                   "dg_add_binary")
+            return
+        x = np.ascontiguousarray(x, np.float32)
         _check(lib().dg_add(self.h, x.shape[0], ids, x), "dg_add")
 
     def add_device(self, ids, x_ptr, n):
@@ -219,13 +266,19 @@ class Index:
             C.c_void_p, np.ctypeslib.ndpointer(np.int32,
                                                flags="C_CONTIGUOUS")]
         st = self.stats()
-        out = np.empty(st["ntotal"], np.int32)
+        # arrival order, tombstoned rows included (dg_export_assign)
+        out = np.empty(st["ntotal"] + st["deleted_count"], np.int32)
         _check(l.dg_export_assign(self.h, out), "dg_export_assign")
         return out
 
     def upsert(self, ids, x):
-        x = np.ascontiguousarray(x, np.float32)
         ids = np.ascontiguousarray(ids, np.int64)
+        if self.is_binary:
+            x = np.ascontiguousarray(x, np.uint8)
+            _check(lib().dg_upsert_binary(self.h, x.shape[0], ids, x),
+                   "dg_upsert_binary")
+            return
+        x = np.ascontiguousarray(x, np.float32)
         _check(lib().dg_upsert(self.h, x.shape[0], ids, x), "dg_upsert")
 
     def remove(self, ids):
@@ -233,11 +286,18 @@ class Index:
         _check(lib().dg_remove(self.h, len(ids), ids), "dg_remove")
 
     def search(self, queries, k, nprobe=0, filt=None):
-        q = np.ascontiguousarray(queries, np.float32)
+        """Binary indexes take np.uint8 [nq, d // 8] queries and return the
+        integer Hamming distance as float32."""
+        q = np.ascontiguousarray(
+            queries, np.uint8 if self.is_binary else np.float32)
         nq = q.shape[0]
         dist = np.empty((nq, k), np.float32)
         ids = np.empty((nq, k), np.int64)
         fp = C.byref(filt) if filt is not None else None
+        if self.is_binary:
+            _check(lib().dg_search_binary(self.h, nq, q, k, nprobe, fp, dist,
+                                          ids), "dg_search_binary")
+            return dist, ids
         _check(lib().dg_search(self.h, nq, q, k, nprobe, fp, dist, ids),
                "dg_search")
         return dist, ids
@@ -246,6 +306,12 @@ class Index:
                       filt=None):
         """Device-pointer hot path (pointers = torch .data_ptr())."""
         fp = C.byref(filt) if filt is not None else None
+        if self.is_binary:
+            _check(lib().dg_search_binary_device(
+                self.h, nq, C.c_void_p(q_ptr), k, nprobe, fp,
+                C.c_void_p(dist_ptr), C.c_void_p(ids_ptr)),
+                "dg_search_binary_device")
+            return
         _check(lib().dg_search_device(self.h, nq, C.c_void_p(q_ptr), k,
                                       nprobe, fp, C.c_void_p(dist_ptr),
                                       C.c_void_p(ids_ptr)),

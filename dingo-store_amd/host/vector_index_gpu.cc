@@ -77,12 +77,29 @@ Status pack(const std::vector<VectorWithId>& v, int32_t dim,
   return Status::OK();
 }
 
+// binary form: binary_values of dim / 8 bytes each; a size mismatch is
+// EVECTOR_INVALID (utils.cc:512)
+Status pack_bits(const std::vector<VectorWithId>& v, int32_t dim,
+                 std::vector<uint8_t>& x, std::vector<int64_t>& ids) {
+  const size_t rb = (size_t)dim / 8;
+  x.resize(v.size() * rb);
+  ids.resize(v.size());
+  for (size_t i = 0; i < v.size(); i++) {
+    if (v[i].vector.binary_values.size() != rb)
+      return {kEVectorInvalid, "binary dimension not match"};
+    memcpy(&x[i * rb], v[i].vector.binary_values.data(), rb);
+    ids[i] = v[i].id;
+  }
+  return Status::OK();
+}
+
 class GpuIndexBase : public VectorIndex {
  public:
   GpuIndexBase(dg_index_kind kind, MetricType metric, int32_t dim,
                int32_t nlist, int device, int32_t pq_m = 0) {
     metric_ = metric;
     dim_ = dim;
+    binary_ = kind == DG_INDEX_BINARY_FLAT || kind == DG_INDEX_BINARY_IVF_FLAT;
     dg_index_desc desc{};
     desc.kind = (int32_t)kind;
     desc.metric = (int32_t)metric;
@@ -116,6 +133,13 @@ class GpuIndexBase : public VectorIndex {
     if (v.empty()) return {kEillegalParamteters, "vector_with_ids is empty"};
     std::vector<float> x;
     std::vector<int64_t> ids;
+    if (binary_) {
+      std::vector<uint8_t> b;
+      Status s = pack_bits(v, dim_, b, ids);
+      if (!s.ok()) return s;
+      return from_dg(
+          dg_add_binary(idx_, (int64_t)v.size(), ids.data(), b.data()));
+    }
     Status s = pack(v, dim_, x, ids);
     if (!s.ok()) return s;
     return from_dg(dg_add(idx_, (int64_t)v.size(), ids.data(), x.data()));
@@ -124,6 +148,13 @@ class GpuIndexBase : public VectorIndex {
     if (v.empty()) return {kEillegalParamteters, "vector_with_ids is empty"};
     std::vector<float> x;
     std::vector<int64_t> ids;
+    if (binary_) {
+      std::vector<uint8_t> b;
+      Status s = pack_bits(v, dim_, b, ids);
+      if (!s.ok()) return s;
+      return from_dg(
+          dg_upsert_binary(idx_, (int64_t)v.size(), ids.data(), b.data()));
+    }
     Status s = pack(v, dim_, x, ids);
     if (!s.ok()) return s;
     return from_dg(dg_upsert(idx_, (int64_t)v.size(), ids.data(), x.data()));
@@ -136,15 +167,25 @@ class GpuIndexBase : public VectorIndex {
     if (v.empty()) return {kEillegalParamteters, "data size invalid"};
     std::vector<float> x;
     std::vector<int64_t> ids;
-    Status s = pack(v, dim_, x, ids);
-    if (!s.ok()) return s;
-    s = from_dg(dg_train(idx_, (int64_t)v.size(), x.data()));
+    Status s;
+    if (binary_) {
+      std::vector<uint8_t> b;
+      s = pack_bits(v, dim_, b, ids);
+      if (!s.ok()) return s;
+      s = from_dg(dg_train_binary(idx_, (int64_t)v.size(), b.data()));
+    } else {
+      s = pack(v, dim_, x, ids);
+      if (!s.ok()) return s;
+      s = from_dg(dg_train(idx_, (int64_t)v.size(), x.data()));
+    }
     if (s.ok()) train_data_size_ = (int64_t)v.size();
     return s;
   }
   Status Train(std::vector<float>& train_datas) override {
     // raw-float Train (vector_index.h:196; size checks per
     // vector_index_ivf_flat.cc:644-652)
+    if (binary_)
+      return {kEVectorNotSupport, "raw-float train on a binary index"};
     size_t data_size = train_datas.size() / dim_;
     if (data_size == 0)
       return {kEillegalParamteters, "data size invalid"};
@@ -185,12 +226,14 @@ class GpuIndexBase : public VectorIndex {
   void LockWrite() override { dg_lock_write(idx_); }
   void UnlockWrite() override { dg_unlock_write(idx_); }
   Status Save(const std::string& path) override {
+    if (binary_) return {kEVectorNotSupport, "binary index save"};
     // the snapshot cycle ships faiss::write_index files
     // (vector_index_snapshot_manager.cc:583-599) — emit the compatible
     // container so CPU nodes can ingest the snapshot
     return from_dg(dg_save_faiss(idx_, path.c_str()));
   }
   Status Load(const std::string& path) override {
+    if (binary_) return {kEVectorNotSupport, "binary index load"};
     dg_index* ni = nullptr;
     dg_status st = dg_load_faiss(&ni, path.c_str(), (int32_t)metric_, -1);
     if (st != DG_OK) return from_dg(st);
@@ -209,8 +252,10 @@ class GpuIndexBase : public VectorIndex {
       return {kEillegalParamteters, "vector_with_ids is empty"};
     if (topk == 0) return Status::OK();
     std::vector<float> x;
+    std::vector<uint8_t> xb;
     std::vector<int64_t> ids;
-    Status s = pack(queries, dim_, x, ids);
+    Status s = binary_ ? pack_bits(queries, dim_, xb, ids)
+                       : pack(queries, dim_, x, ids);
     if (!s.ok()) return s;
 
     dg_filter df{};
@@ -224,12 +269,16 @@ class GpuIndexBase : public VectorIndex {
         return {kEVectorNotSupport, "composite filters via reader fallback"};
       }
     }
-    int32_t nprobe = p.ivf_flat_nprobe;
+    int32_t nprobe = binary_ ? p.binary_ivf_flat_nprobe : p.ivf_flat_nprobe;
     std::vector<float> dist((size_t)queries.size() * topk);
     std::vector<int64_t> labels((size_t)queries.size() * topk, -1);
-    dg_status st = dg_search(idx_, (int64_t)queries.size(), x.data(),
-                             (int32_t)topk, nprobe, dfp, dist.data(),
-                             labels.data());
+    dg_status st =
+        binary_ ? dg_search_binary(idx_, (int64_t)queries.size(), xb.data(),
+                                   (int32_t)topk, nprobe, dfp, dist.data(),
+                                   labels.data())
+                : dg_search(idx_, (int64_t)queries.size(), x.data(),
+                            (int32_t)topk, nprobe, dfp, dist.data(),
+                            labels.data());
     if (st != DG_OK) return from_dg(st);
     // FillSearchResult shaping (utils.cc:612-655)
     results.clear();
@@ -242,9 +291,11 @@ class GpuIndexBase : public VectorIndex {
         vd.vector_with_id.id = labels[pos];
         vd.vector_with_id.vector.dimension = dim_;
         vd.metric_type = metric_;
-        vd.distance = (metric_ == MetricType::kL2)
+        // L2 and Hamming (:640-650) pass through; IP/cosine flip, :634
+        vd.distance = (metric_ == MetricType::kL2 ||
+                       metric_ == MetricType::kHamming)
                           ? dist[pos]
-                          : 1.0f - dist[pos];  // the flip, :634
+                          : 1.0f - dist[pos];
         results[row].vector_with_distances.push_back(std::move(vd));
       }
     }
@@ -258,6 +309,7 @@ class GpuIndexBase : public VectorIndex {
     // mirrors VectorIndexIvfFlat::RangeSearch: for IP/cosine the dingo
     // radius converts to a faiss score threshold 1 - r
     // (src/vector/vector_index_ivf_flat.cc:302-305)
+    if (binary_) return {kEVectorNotSupport, "binary index range search"};
     if (queries.empty())
       return {kEillegalParamteters, "vector_with_ids is empty"};
     std::vector<float> x;
@@ -302,6 +354,7 @@ class GpuIndexBase : public VectorIndex {
   dg_status create_st_ = DG_OK;
   MetricType metric_;
   int32_t dim_;
+  bool binary_ = false;
   int64_t train_data_size_ = 0;
 };
 
@@ -336,6 +389,23 @@ class GpuIvfFlatIndex : public GpuIndexBase {
 
  private:
   int64_t nlist_org_;
+};
+
+class GpuBinaryFlatIndex : public GpuIndexBase {
+ public:
+  GpuBinaryFlatIndex(int32_t d, int dev)
+      : GpuIndexBase(DG_INDEX_BINARY_FLAT, MetricType::kHamming, d, 0, dev) {}
+  bool NeedTrain() override { return false; }
+  bool SupportSave() override { return false; }
+};
+
+class GpuBinaryIvfFlatIndex : public GpuIndexBase {
+ public:
+  GpuBinaryIvfFlatIndex(int32_t d, int32_t nlist, int dev)
+      : GpuIndexBase(DG_INDEX_BINARY_IVF_FLAT, MetricType::kHamming, d, nlist,
+                     dev) {}
+  bool NeedTrain() override { return !IsTrained(); }
+  bool SupportSave() override { return false; }
 };
 
 class GpuIvfPqIndex : public GpuIndexBase {
@@ -459,6 +529,20 @@ std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
                                            int32_t nsubvector, int device) {
   auto p = std::make_unique<GpuIvfPqIndex>(metric, dim, ncentroids,
                                            nsubvector, device);
+  if (!p->CreateStatus().ok()) return nullptr;
+  return p;
+}
+
+std::unique_ptr<VectorIndex> NewBinaryFlatIndex(int32_t dim, int device) {
+  auto p = std::make_unique<GpuBinaryFlatIndex>(dim, device);
+  if (!p->CreateStatus().ok()) return nullptr;
+  return p;
+}
+
+std::unique_ptr<VectorIndex> NewBinaryIvfFlatIndex(int32_t dim,
+                                                   int32_t ncentroids,
+                                                   int device) {
+  auto p = std::make_unique<GpuBinaryIvfFlatIndex>(dim, ncentroids, device);
   if (!p->CreateStatus().ok()) return nullptr;
   return p;
 }
@@ -721,5 +805,96 @@ extern "C" int dg_mirror_selftest(void) {
         return 80;
   }
   DG_ST("done");
+  return 0;
+}
+
+// ---------------- self-test, binary indexes (GPU) ----------------
+extern "C" int dg_mirror_selftest_binary(void) {
+  using namespace dingogpu;
+  const int32_t d = 200, n = 1500;  // 25 bytes: word + tail per row
+  std::vector<VectorWithId> batch(n);
+  uint32_t s = 4242;
+  for (int i = 0; i < n; i++) {
+    batch[i].id = i * 3 + 1;
+    batch[i].vector.dimension = d;
+    batch[i].vector.value_type = ValueType::kUint8;
+    batch[i].vector.binary_values.resize(d / 8);
+    for (int j = 0; j < d / 8; j++) {
+      s = s * 1664525u + 1013904223u;
+      batch[i].vector.binary_values[j] = (uint8_t)(s >> 24);
+    }
+  }
+  auto hamming = [&](const VectorWithId& a, const VectorWithId& b) {
+    int h = 0;
+    for (int j = 0; j < d / 8; j++)
+      h += __builtin_popcount(a.vector.binary_values[j] ^
+                              b.vector.binary_values[j]);
+    return h;
+  };
+  for (int kind = 0; kind < 2; kind++) {
+    auto idx = kind == 0 ? NewBinaryFlatIndex(d) : NewBinaryIvfFlatIndex(d, 8);
+    if (!idx) return 100 + kind;
+    if (idx->GetMetricType() != MetricType::kHamming) return 102;
+    VectorSearchParameter p;
+    p.binary_ivf_flat_nprobe = 8;
+    if (kind == 1) {
+      if (idx->IsTrained() || !idx->NeedTrain()) return 103;
+      if (!idx->Train(batch).ok()) return 104;
+      if (!idx->IsTrained()) return 105;
+    }
+    if (!idx->Add(batch).ok()) return 106;
+    int64_t cnt = 0;
+    if (!idx->GetCount(cnt).ok() || cnt != n) return 107;
+    std::vector<VectorWithId> queries(batch.begin(), batch.begin() + 40);
+    std::vector<VectorWithDistanceResult> res;
+    if (!idx->Search(queries, 4, {}, false, p, res).ok()) return 108;
+    if (res.size() != queries.size()) return 109;
+    for (size_t i = 0; i < queries.size(); i++) {
+      auto& r = res[i].vector_with_distances;
+      if (r.size() != 4) return 110;
+      // self top-1 at distance 0 (random 200-bit rows are distinct)
+      if (r[0].vector_with_id.id != queries[i].id || r[0].distance != 0.f)
+        return 111;
+      // Hamming pass-through: the reported distance is the integer
+      // distance to the returned row, ascending, not flipped
+      for (size_t j = 0; j < r.size(); j++) {
+        const int64_t row = (r[j].vector_with_id.id - 1) / 3;
+        if (row < 0 || row >= n) return 112;
+        if (r[j].distance != (float)hamming(queries[i], batch[row]))
+          return 113;
+        if (j && r[j].distance < r[j - 1].distance) return 114;
+        if (r[j].metric_type != MetricType::kHamming) return 115;
+      }
+    }
+    // wrong byte count is rejected
+    VectorWithId bad = batch[0];
+    bad.id = 999999;
+    bad.vector.binary_values.resize(d / 8 - 1);
+    if (idx->Add({bad}).code != kEVectorInvalid) return 116;
+    if (idx->Search({bad}, 1, {}, false, p, res).code != kEVectorInvalid)
+      return 117;
+    // delete then search: the row is gone
+    if (!idx->Delete({batch[5].id}).ok()) return 118;
+    if (!idx->Search({batch[5]}, 1, {}, false, p, res).ok()) return 119;
+    if (!res[0].vector_with_distances.empty() &&
+        res[0].vector_with_distances[0].vector_with_id.id == batch[5].id)
+      return 120;
+    if (!idx->Upsert({batch[5]}).ok()) return 121;
+    if (!idx->Search({batch[5]}, 1, {}, false, p, res).ok()) return 122;
+    if (res[0].vector_with_distances.empty() ||
+        res[0].vector_with_distances[0].vector_with_id.id != batch[5].id)
+      return 123;
+    // out of scope for the binary kinds
+    std::vector<VectorWithDistanceResult> rr;
+    if (idx->RangeSearch(queries, 10.f, {}, false, p, rr).code !=
+        kEVectorNotSupport)
+      return 124;
+    if (idx->Save("/tmp/dg_mirror_selftest_binary.idx").code !=
+        kEVectorNotSupport)
+      return 125;
+    if (idx->Load("/tmp/dg_mirror_selftest_binary.idx").code !=
+        kEVectorNotSupport)
+      return 126;
+  }
   return 0;
 }

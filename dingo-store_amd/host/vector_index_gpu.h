@@ -22,13 +22,20 @@ namespace dingogpu {
 // ---- pb::common::* re-declarations (schema absent; field set from call
 // sites, e.g. ExtractVectorValue src/vector/vector_index_utils.cc:564-609,
 // FillSearchResult :612-655) ----
-enum class MetricType { kL2 = 0, kInnerProduct = 1, kCosine = 2 };
+enum class MetricType {
+  kL2 = 0,
+  kInnerProduct = 1,
+  kCosine = 2,
+  kHamming = 3  // binary indexes only
+};
 enum class ValueType { kFloat = 0, kUint8 = 1 };
 
 struct Vector {
   int32_t dimension = 0;
   ValueType value_type = ValueType::kFloat;
   std::vector<float> float_values;
+  // ValueType::kUint8: dimension / 8 packed bytes (binary indexes)
+  std::vector<uint8_t> binary_values;
 };
 
 struct VectorWithId {
@@ -52,6 +59,7 @@ struct VectorSearchParameter {
   bool without_vector_data = true;
   int32_t ivf_flat_nprobe = 0;  // parameter.ivf_flat().nprobe()
   int32_t ivf_pq_nprobe = 0;
+  int32_t binary_ivf_flat_nprobe = 0;  // parameter.binary_ivf_flat().nprobe()
   bool enable_range_search = false;
   float radius = 0.f;
 };
@@ -225,6 +233,15 @@ std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
                                            int32_t nsubvector,
                                            int device = -1);
 
+// Binary (Hamming) indexes: dim in bits, vectors carry binary_values of
+// dim / 8 bytes; distances are the integer Hamming distance, passed through
+// (vector_index_utils.cc:640-650).  RangeSearch, Save and Load return
+// kEVectorNotSupport.
+std::unique_ptr<VectorIndex> NewBinaryFlatIndex(int32_t dim, int device = -1);
+std::unique_ptr<VectorIndex> NewBinaryIvfFlatIndex(int32_t dim,
+                                                   int32_t ncentroids,
+                                                   int device = -1);
+
 }  // namespace dingogpu
 
 extern "C" {
@@ -232,4 +249,7 @@ extern "C" {
 // verifies the dingo-store observable semantics (1 - score flip for
 // IP/cosine, vector_index_utils.cc:634; self-top-1).  Returns 0 on success.
 int dg_mirror_selftest(void);
+// Same for the binary indexes: Flat and IVF-Flat through the mirror, self
+// top-1 at distance 0 and the Hamming distance passed through unflipped.
+int dg_mirror_selftest_binary(void);
 }

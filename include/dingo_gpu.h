@@ -56,15 +56,23 @@ typedef enum dg_index_kind {
                             src/vector/vector_index_flat.cc:81-98 */
   DG_INDEX_IVF_FLAT = 1, /* VectorIndexIvfFlat: faiss IndexIVFFlat,
                             src/vector/vector_index_ivf_flat.cc:805-823 */
-  DG_INDEX_IVF_PQ = 2    /* VectorIndexRawIvfPq: faiss IndexIVFPQ,
+  DG_INDEX_IVF_PQ = 2,   /* VectorIndexRawIvfPq: faiss IndexIVFPQ,
                             src/vector/vector_index_raw_ivf_pq.cc:551-570 */
+  DG_INDEX_BINARY_FLAT = 3,     /* VectorIndexFlat<faiss::IndexBinary,
+                                   IndexBinaryIDMap2>,
+                                   src/vector/vector_index_flat.cc:71,99-102 */
+  DG_INDEX_BINARY_IVF_FLAT = 4  /* VectorIndexIvfFlat<faiss::IndexBinary,
+                                   IndexBinaryIVF>,
+                                   src/vector/vector_index_ivf_flat.cc:62,75-80 */
 } dg_index_kind;
 
 typedef enum dg_metric {
   DG_METRIC_L2 = 0,     /* METRIC_TYPE_L2 */
   DG_METRIC_IP = 1,     /* METRIC_TYPE_INNER_PRODUCT */
-  DG_METRIC_COSINE = 2  /* METRIC_TYPE_COSINE = normalize + IP,
+  DG_METRIC_COSINE = 2, /* METRIC_TYPE_COSINE = normalize + IP,
                            src/vector/vector_index_flat.cc:88-91 */
+  DG_METRIC_HAMMING = 3 /* METRIC_TYPE_HAMMING: the binary kinds only (and
+                           their only metric, vector_index_utils.cc:1094,1125) */
 } dg_metric;
 
 typedef struct dg_index dg_index; /* opaque */
@@ -72,7 +80,8 @@ typedef struct dg_index dg_index; /* opaque */
 typedef struct dg_index_desc {
   int32_t kind;      /* dg_index_kind */
   int32_t metric;    /* dg_metric */
-  int32_t d;         /* dimension */
+  int32_t d;         /* dimension (binary kinds: in BITS, d % 8 == 0,
+                        8 <= d <= 32768) */
   int32_t nlist;     /* IVF: ncentroids (reference default 2048,
                         src/vector/vector_index.h "kCreateIvfFlatParamNcentroids") */
   int32_t pq_m;      /* IVF-PQ: subquantizers (default 64) */
@@ -231,6 +240,42 @@ dg_status dg_load(dg_index** out, const char* path, int32_t device);
 dg_status dg_save_faiss(dg_index* idx, const char* path);
 dg_status dg_load_faiss(dg_index** out, const char* path,
                         int32_t metric_override, int32_t device);
+
+/* ---- binary (Hamming) indexes ----
+ * DG_INDEX_BINARY_FLAT / DG_INDEX_BINARY_IVF_FLAT with DG_METRIC_HAMMING.
+ * Rows, queries and centroids are bit vectors of desc.d bits, passed as
+ * uint8 with a row stride of d/8 bytes (bit j = byte j/8, bit j%8).  The
+ * calls restate the float ones above at the reference's binary call sites
+ * (vector_index_flat.cc:151-153,224-239; vector_index_ivf_flat.cc:122-123,
+ * 207-209,254-257,578-635): train unpacks to +-1 floats, runs the same
+ * k-means and binarises the centroids with > 0; an IVF nlist <= 0 defaults
+ * to 2048, nprobe <= 0 to 80.  out_dist holds the exact integer Hamming
+ * distance as float32, passed through with no flip
+ * (vector_index_utils.cc:640-650); ties on distance resolve toward the
+ * smaller internal row, ties between lists toward the smaller list.
+ * nq is limited to 261887 per call.  dg_remove, dg_export_assign,
+ * dg_set_list_mask, dg_stats (d in bits), dg_sync, the write lock and
+ * dg_index_destroy work unchanged.  The float entry points return
+ * DG_EINVAL on a binary index and these return DG_EINVAL on a float one;
+ * dg_range_search, dg_save and dg_save_faiss return DG_ENOT_SUPPORT on a
+ * binary index. */
+dg_status dg_train_binary(dg_index* idx, int64_t n, const uint8_t* x);
+dg_status dg_set_centroids_binary(dg_index* idx, int32_t nlist,
+                                  const uint8_t* centroids);
+dg_status dg_get_centroids_binary(dg_index* idx, uint8_t* out_centroids);
+dg_status dg_add_binary(dg_index* idx, int64_t n, const int64_t* ids,
+                        const uint8_t* x);
+dg_status dg_upsert_binary(dg_index* idx, int64_t n, const int64_t* ids,
+                           const uint8_t* x);
+dg_status dg_search_binary(dg_index* idx, int64_t nq, const uint8_t* x,
+                           int32_t k, int32_t nprobe, const dg_filter* filter,
+                           float* out_dist /* nq x k */,
+                           int64_t* out_ids /* nq x k */);
+/* device pointers, no synchronization, runs on the index stream */
+dg_status dg_search_binary_device(dg_index* idx, int64_t nq,
+                                  const uint8_t* d_x, int32_t k,
+                                  int32_t nprobe, const dg_filter* filter,
+                                  float* d_out_dist, int64_t* d_out_ids);
 
 /* ---- multi-GPU sharding support ----
  * Each rank holds a shard of the database (row-sharded)
