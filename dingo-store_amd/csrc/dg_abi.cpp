@@ -275,6 +275,13 @@ static dg_status sgemm_dots(dg_index* ix, const float* X, int64_t rows,
 }
 
 // ---------------- create / destroy ----------------
+extern "C" int32_t dg_ivfpq_max_m(int32_t device) {
+  if (device < 0 || device >= dg_device_count()) return 0;
+  DeviceGuard g(device);
+  const size_t per_m = dgk::ivfpq_scan_lds(dgk::kPqTileRows, 1);
+  return (int32_t)(dgk::max_launch_lds() / per_m) & ~3;  // m % 4 == 0
+}
+
 extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   if (!out || !dp) {
     dg_set_error("null arg");
@@ -336,6 +343,18 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   if (dg_device_count() == 0) {
     dg_set_error("no HIP device (the GPU path has no CPU fallback)");
     return DG_ENOGPU;
+  }
+  if (desc.kind == DG_INDEX_IVF_PQ) {
+    // the scan stages a code tile and the list's f16 S table in LDS; an m
+    // whose default tile cannot be launched has no scan at all
+    const int32_t max_m = dg_ivfpq_max_m(desc.device >= 0 ? desc.device : 0);
+    if (desc.pq_m > max_m) {
+      dg_set_error("IVF-PQ m=%d unsupported: the scan needs %zu bytes of LDS "
+                   "per block, this device launches m <= %d",
+                   desc.pq_m,
+                   dgk::ivfpq_scan_lds(dgk::kPqTileRows, desc.pq_m), max_m);
+      return DG_ENOT_SUPPORT;
+    }
   }
   dg_index* ix = new dg_index();
   ix->desc = desc;
@@ -405,6 +424,8 @@ extern "C" void dg_index_destroy(dg_index* ix) {
 }
 
 // ---------------- centroids ----------------
+static dg_status finish_pq_tables(dg_index* ix);
+
 extern "C" dg_status dg_set_centroids(dg_index* ix, int32_t nlist,
                                       const float* centroids) {
   if (!ix || !centroids) return DG_EINVAL;
@@ -435,6 +456,10 @@ extern "C" dg_status dg_set_centroids(dg_index* ix, int32_t nlist,
   ix->trained = true;
   ix->csr_valid = false;
   ix->index_gen++;
+  // S = ||c_sub + cb||^2 is built from the centroids: new centroids under
+  // existing codebooks need new tables, or every L2 distance is off
+  if (ix->desc.kind == DG_INDEX_IVF_PQ && ix->pq_trained)
+    return finish_pq_tables(ix);
   return DG_OK;
 }
 
@@ -684,11 +709,30 @@ static dg_status finish_pq_tables(dg_index* ix) {
       (st = dbuf_reserve(ix->d_cb_norms, (size_t)M * 256 * 4, ix->stream,
                          false)) != DG_OK)
     return st;
+  // S is stored as f16: an entry above 65504 would become inf and turn
+  // every key of its list into inf/NaN, so k_build_S flags it and the
+  // tables are refused (train/load time only, never on the search path)
+  dg_dbuf d_flag{};
+  DbufGuard g_flag(d_flag);
+  if ((st = dbuf_reserve(d_flag, 4, ix->stream, false)) != DG_OK) return st;
+  DG_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, ix->stream));
   dgk::build_S(ix->stream, (const float*)ix->d_centroids.p,
                (const float*)ix->d_codebooks.p, nlist, M, dsub, d,
-               (__half*)ix->d_S.p);
+               (__half*)ix->d_S.p, (int32_t*)d_flag.p);
   dgk::row_norms(ix->stream, (const float*)ix->d_codebooks.p,
                  (int64_t)M * 256, dsub, (float*)ix->d_cb_norms.p);
+  int32_t overflow = 0;
+  DG_HIP_CHECK(hipMemcpyAsync(&overflow, d_flag.p, 4, hipMemcpyDeviceToHost,
+                              ix->stream));
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  if (overflow) {
+    ix->pq_trained = false;  // d_S holds inf/NaN; do not search with it
+    dg_set_error(
+        "IVF-PQ table overflow: ||centroid_sub + codeword||^2 exceeds the "
+        "f16 limit 65504 for some (list, subspace, code); scale the vectors "
+        "down (the same limit holds for |query_sub . codeword|)");
+    return DG_ENOT_SUPPORT;
+  }
   return DG_OK;
 }
 
@@ -1235,12 +1279,15 @@ extern "C" dg_status dg_set_list_mask(dg_index* ix, const uint8_t* mask) {
   if (!ix) return DG_EINVAL;
   std::unique_lock lk(ix->rw);
   DeviceGuard g(ix->device);
+  // a captured small-batch graph holds the mask pointer it was captured
+  // with (null without a mask): setting or clearing one must recapture
+  ix->index_gen++;
   if (!mask) {
     ix->has_mask = false;
     return DG_OK;
   }
-  if (ix->desc.kind != DG_INDEX_IVF_FLAT &&
-      ix->desc.kind != DG_INDEX_BINARY_IVF_FLAT) {
+  // every IVF kind: the probe kernels that apply the mask are shared
+  if (dg_kind_is_flat(ix->desc.kind)) {
     dg_set_error("list mask on non-IVF index");
     return DG_EINVAL;
   }
@@ -1936,13 +1983,14 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
       }
       dgk::f32_to_f16(ix->stream, (const float*)ix->ws_Tf32.p,
                       (int64_t)nq * M * 256, (__half*)ix->ws_T.p);
-      dgk::ivfpq_scan(ix->stream, units, total_units,
-                      (const int64_t*)ix->d_csr_offsets.p,
-                      (const uint8_t*)ix->d_csr_codes.p,
-                      (const __half*)ix->d_S.p, (const __half*)ix->ws_T.p,
-                      (const float*)ix->ws_dots.p, nlist, M, inv_offsets32,
-                      inv_q, inv_rank, qp_off, q_cand_base, np, metric,
-                      d_bitmap, chunk_rows, (uint64_t*)ix->ws_cand.p);
+      // a scan that did not launch leaves ws_cand stale; never select on it
+      DG_HIP_CHECK(dgk::ivfpq_scan(
+          ix->stream, units, total_units,
+          (const int64_t*)ix->d_csr_offsets.p,
+          (const uint8_t*)ix->d_csr_codes.p, (const __half*)ix->d_S.p,
+          (const __half*)ix->ws_T.p, (const float*)ix->ws_dots.p, nlist, M,
+          inv_offsets32, inv_q, inv_rank, qp_off, q_cand_base, np, metric,
+          d_bitmap, chunk_rows, (uint64_t*)ix->ws_cand.p));
     } else {
       // THE scan (columnar v2)
       char* mp = (char*)ix->d_chunk_meta.p;

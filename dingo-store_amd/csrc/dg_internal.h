@@ -332,16 +332,24 @@ void set_code(hipStream_t s, const int32_t* amin, int64_t n, int32_t m,
 void gather_codes(hipStream_t s, const uint8_t* src, const uint32_t* perm,
                   int64_t n, int32_t M, uint8_t* dst);
 void build_S(hipStream_t s, const float* centroids, const float* codebooks,
-             int32_t nlist, int32_t M, int32_t dsub, int32_t d, __half* S);
+             int32_t nlist, int32_t M, int32_t dsub, int32_t d, __half* S,
+             int32_t* overflow);  // *overflow |= 1 if an entry exceeds f16
+// rows of the default k_ivfpq_scan tile (RPV=4 x 64 lanes)
+constexpr int32_t kPqTileRows = 256;
+size_t max_launch_lds();  // dynamic LDS per launch, current device
+size_t ivfpq_scan_lds(int32_t tile_rows, int32_t M);
 void f32_to_f16(hipStream_t s, const float* in, int64_t n, __half* out);
-void ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
-                const int64_t* csr_offsets, const uint8_t* csr_codes,
-                const __half* S, const __half* T, const float* coarse_dots,
-                int32_t nlist, int32_t M, const int32_t* inv_offsets,
-                const int32_t* inv_q, const int32_t* inv_rank,
-                const int64_t* qp_off, const int64_t* q_cand_base,
-                int32_t nprobe, int metric, const uint32_t* bitmap,
-                int32_t chunk_rows, uint64_t* cand);
+// returns the launch status; no launch is issued if the tile's LDS does
+// not fit the device
+hipError_t ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
+                      const int64_t* csr_offsets, const uint8_t* csr_codes,
+                      const __half* S, const __half* T,
+                      const float* coarse_dots, int32_t nlist, int32_t M,
+                      const int32_t* inv_offsets, const int32_t* inv_q,
+                      const int32_t* inv_rank, const int64_t* qp_off,
+                      const int64_t* q_cand_base, int32_t nprobe, int metric,
+                      const uint32_t* bitmap, int32_t chunk_rows,
+                      uint64_t* cand);
 // emit: resolve ids, apply metric convention
 void emit_results(hipStream_t s, const uint64_t* topk,
                   const int64_t* ids_lookup, const float* qnorms, int64_t nq,

@@ -756,10 +756,13 @@ __global__ void k_gather_codes(const uint8_t* __restrict__ src,
   for (int j = sub; j < M / 4; j += 32) t[j] = s[j];
 }
 
+static constexpr float kHalfMax = 65504.0f;  // largest finite f16
+
 __global__ void k_build_S(const float* __restrict__ centroids,
                           const float* __restrict__ codebooks, int32_t nlist,
                           int32_t M, int32_t dsub, int32_t d,
-                          __half* __restrict__ S) {
+                          __half* __restrict__ S,
+                          int32_t* __restrict__ overflow) {
   // one thread per (l, m, code): ||c_sub + cb||^2 over dsub elems
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t total = (int64_t)nlist * M * 256;
@@ -774,6 +777,9 @@ __global__ void k_build_S(const float* __restrict__ centroids,
     float t = c[j] + cb[j];
     acc += t * t;
   }
+  // an entry f16 cannot hold (it would round to inf, or is NaN already)
+  // poisons every key of its list: raise the flag the host reads back
+  if (!(acc <= kHalfMax)) atomicOr(overflow, 1);
   S[i] = __float2half(acc);
 }
 
@@ -2856,10 +2862,28 @@ void gather_codes(hipStream_t s, const uint8_t* src, const uint32_t* perm,
 }
 
 void build_S(hipStream_t s, const float* centroids, const float* codebooks,
-             int32_t nlist, int32_t M, int32_t dsub, int32_t d, __half* S) {
+             int32_t nlist, int32_t M, int32_t dsub, int32_t d, __half* S,
+             int32_t* overflow) {
   int64_t total = (int64_t)nlist * M * 256;
   hipLaunchKernelGGL(k_build_S, dim3(ceil_div(total, 256)), dim3(256), 0, s,
-                     centroids, codebooks, nlist, M, dsub, d, S);
+                     centroids, codebooks, nlist, M, dsub, d, S, overflow);
+}
+
+// dynamic LDS one launch may ask for on the current device (160 KiB on
+// MI355X); 0 if the query fails, which rejects every IVF-PQ geometry
+size_t max_launch_lds() {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock,
+                            dev) != hipSuccess ||
+      v < 0)
+    return 0;
+  return (size_t)v;
+}
+
+// LDS of one k_ivfpq_scan block: the staged code tile + the f16 S_l table
+size_t ivfpq_scan_lds(int32_t tile_rows, int32_t M) {
+  return (size_t)tile_rows * M + (size_t)M * 256 * 2;
 }
 
 void f32_to_f16(hipStream_t s, const float* in, int64_t n, __half* out) {
@@ -2867,15 +2891,16 @@ void f32_to_f16(hipStream_t s, const float* in, int64_t n, __half* out) {
                             0, s, in, n, out);
 }
 
-void ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
-                const int64_t* csr_offsets, const uint8_t* csr_codes,
-                const __half* S, const __half* T, const float* coarse_dots,
-                int32_t nlist, int32_t M, const int32_t* inv_offsets,
-                const int32_t* inv_q, const int32_t* inv_rank,
-                const int64_t* qp_off, const int64_t* q_cand_base,
-                int32_t nprobe, int metric, const uint32_t* bitmap,
-                int32_t chunk_rows, uint64_t* cand) {
-  if (!n_units) return;
+hipError_t ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
+                      const int64_t* csr_offsets, const uint8_t* csr_codes,
+                      const __half* S, const __half* T,
+                      const float* coarse_dots, int32_t nlist, int32_t M,
+                      const int32_t* inv_offsets, const int32_t* inv_q,
+                      const int32_t* inv_rank, const int64_t* qp_off,
+                      const int64_t* q_cand_base, int32_t nprobe, int metric,
+                      const uint32_t* bitmap, int32_t chunk_rows,
+                      uint64_t* cand) {
+  if (!n_units) return hipSuccess;
   // T-table (L2/L3) traffic per chunk scales as 1/TILE: every staged tile
   // walks each probing query's 48 KB T window once, so the largest tile
   // whose codes + S_l fit LDS wins unless occupancy dominates (A/B'd;
@@ -2883,15 +2908,23 @@ void ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
   const char* e = getenv("DG_PQ_RPV");
   int rpv = e ? atoi(e) : 4;  // 256-row tiles + 2 blocks/CU measured best
   if (rpv != 4 && rpv != 6 && rpv != 8 && rpv != 16 && rpv != 17) rpv = 4;
-  size_t lds = (size_t)(rpv == 6 ? 4 : (rpv == 17 ? 16 : rpv)) * 64 * M +
-               (size_t)M * 256 * 2;  // codes + f16 S_l
+  auto tile_lds = [&](int r) {
+    return ivfpq_scan_lds((r == 6 ? 4 : (r == 17 ? 16 : r)) * WAVE, M);
+  };
+  // a forced tile that does not fit falls back to the default one, whose
+  // fit dg_index_create has checked (kPqTileRows)
+  const size_t lds_max = max_launch_lds();
+  if (tile_lds(rpv) > lds_max) rpv = 4;
+  const size_t lds = tile_lds(rpv);
+  if (lds > lds_max) return hipErrorInvalidValue;  // never issue the launch
+  (void)hipGetLastError();  // the status read below is this launch's own
   if (rpv == 17) {  // cooperative: 4 waves share each query's T window
     hipLaunchKernelGGL((k_ivfpq_scan<16, 1, true>), dim3((uint32_t)n_units),
                        dim3(256), lds, s, units, csr_offsets, csr_codes, S,
                        T, coarse_dots, nlist, M, inv_offsets, inv_q,
                        inv_rank, qp_off, q_cand_base, nprobe, metric, bitmap,
                        chunk_rows, cand);
-    return;
+    return hipGetLastError();
   }
   if (rpv == 6)  // round-1 form: VGPRs capped at 80 by launch_bounds(256,6)
     hipLaunchKernelGGL((k_ivfpq_scan<4, 6>), dim3((uint32_t)n_units),
@@ -2918,6 +2951,7 @@ void ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
                        T, coarse_dots, nlist, M, inv_offsets, inv_q,
                        inv_rank, qp_off, q_cand_base, nprobe, metric, bitmap,
                        chunk_rows, cand);
+  return hipGetLastError();
 }
 
 void transpose_chunks(hipStream_t s, const uint32_t* units, int32_t n_units,

@@ -139,6 +139,14 @@ def device_count():
     return lib().dg_device_count()
 
 
+def ivfpq_max_m(device=0):
+    """Largest IVF-PQ m whose scan tile fits the device's LDS."""
+    l = lib()
+    l.dg_ivfpq_max_m.argtypes = [C.c_int32]
+    l.dg_ivfpq_max_m.restype = C.c_int32
+    return l.dg_ivfpq_max_m(device)
+
+
 def make_filter(kind=0, negate=False, min_id=0, max_id=0, ids=None,
                 bitmap=None, bitmap_base=0):
     f = _Filter()

@@ -153,7 +153,8 @@ void dg_index_destroy(dg_index* idx);
  * seed 1234) restated in oracle/oracle.c and matched here. ---- */
 dg_status dg_train(dg_index* idx, int64_t n, const float* x);
 /* Inject/extract centroids so CPU oracle and GPU search identical structures
- * (BASELINE.md protocol).  set_centroids marks the index trained. */
+ * (BASELINE.md protocol).  set_centroids marks the index trained; on an
+ * IVF-PQ index that has codebooks it rebuilds the ADC tables. */
 dg_status dg_set_centroids(dg_index* idx, int32_t nlist, const float* centroids);
 dg_status dg_get_centroids(dg_index* idx, float* out_centroids);
 /* IVF-PQ codebook injection/extraction (m x 256 x (d/m) floats), the PQ
@@ -162,6 +163,15 @@ dg_status dg_get_centroids(dg_index* idx, float* out_centroids);
 dg_status dg_set_codebooks(dg_index* idx, int32_t m, int32_t nbits,
                            const float* codebooks);
 dg_status dg_get_codebooks(dg_index* idx, float* out_codebooks);
+/* IVF-PQ limits.  The scan keeps a 256-row code tile and one list's f16
+ * table in LDS, 768 * m bytes per block: dg_index_create, dg_load and
+ * dg_load_faiss return DG_ENOT_SUPPORT for m above dg_ivfpq_max_m(device)
+ * (212 with the 160 KiB a launch may use on MI355X; 0 if there is no such
+ * device).  The tables are f16: dg_set_codebooks, dg_train and the loaders
+ * return DG_ENOT_SUPPORT if some ||centroid_sub + codeword||^2 exceeds
+ * 65504.  |query_sub . codeword| has the same limit but is not checked
+ * (IVF-PQ limits). */
+int32_t dg_ivfpq_max_m(int32_t device);
 
 /* ---- mutation (exclusive) ----
  * add restates faiss add_with_ids via VectorIndexIvfFlat::Add
