@@ -86,6 +86,15 @@ static bool scan_fused_enabled() {
   return !(e && e[0] == '0' && e[1] == '\0');
 }
 
+// Blocks per launch of the binary Flat range kernel; more columns than that
+// covers are scanned in several launches.  DG_RANGE_SPAN_BLOCKS lowers it
+// so that tests reach the multi-launch path at small sizes (read per call).
+static int64_t range_span_blocks() {
+  const char* e = getenv("DG_RANGE_SPAN_BLOCKS");
+  const long long v = e ? atoll(e) : 0;
+  return v > 0 ? std::min<long long>(v, 1ll << 30) : 1ll << 30;
+}
+
 static void dbuf_free(dg_dbuf& b) {
   if (b.p) (void)hipFree(b.p);
   b = {};
@@ -1195,6 +1204,41 @@ dg_status dg_ingest_rows(dg_index* ix, int64_t n, const int64_t* ids,
   return DG_OK;
 }
 
+dg_status dg_ingest_bits(dg_index* ix, int64_t n, const int64_t* ids,
+                         const uint8_t* bits, const int32_t* assign) {
+  if (!ix || !ix->is_bin || !ids || !bits || n <= 0) return DG_EINVAL;
+  std::unique_lock lk(ix->rw);
+  DeviceGuard g(ix->device);
+  const int64_t n0 = ix->ntotal;
+  dg_status st =
+      dbuf_reserve(ix->d_ids, (size_t)(n0 + n) * 8, ix->stream, true);
+  if (st == DG_OK)
+    st = dbuf_reserve(ix->d_assign, (size_t)(n0 + n) * 4, ix->stream, true);
+  if (st == DG_OK)
+    st = dbuf_reserve(ix->d_codes, (size_t)(n0 + n) * ix->b_wp * 4,
+                      ix->stream, true);
+  if (st != DG_OK) return st;
+  st = upload_bits_padded(ix, (uint32_t*)ix->d_codes.p + (size_t)n0 * ix->b_wp,
+                          bits, n, false);
+  if (st != DG_OK) return st;
+  DG_HIP_CHECK(hipMemcpyAsync((int64_t*)ix->d_ids.p + n0, ids, (size_t)n * 8,
+                              hipMemcpyHostToDevice, ix->stream));
+  if (assign) {
+    DG_HIP_CHECK(hipMemcpyAsync((int32_t*)ix->d_assign.p + n0, assign,
+                                (size_t)n * 4, hipMemcpyHostToDevice,
+                                ix->stream));
+  } else {
+    dgk::iota_i32(ix->stream, (int32_t*)ix->d_assign.p + n0, n, 0);
+  }
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] >= 0) ix->id_count.emplace(ids[i], 1);
+  ix->ntotal += n;
+  ix->csr_valid = false;
+  ix->index_gen++;
+  return DG_OK;
+}
+
 extern "C" dg_status dg_add_device(dg_index* ix, int64_t n,
                                    const int64_t* ids, const float* d_x) {
   return add_impl(ix, n, ids, d_x, true, false, "dg_add_device");
@@ -1481,7 +1525,8 @@ static uint32_t h_enc_f32(float x) {
 }
 
 struct dg_range_req {  // when set, search_core does radius search instead
-  float radius;        // faiss convention: L2 dist < r; IP score > r
+  float radius;        // faiss convention: L2 dist < r; IP score > r;
+                       // Hamming: integer dist < r (clamped, exact in f32)
   int64_t* lims;       // caller's nq+1
   int64_t** out_ids;   // malloc'd here
   float** out_dists;
@@ -1511,6 +1556,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
   };
 
   if (!ix->capturing) (void)hipEventRecord(ix->ev[0], ix->stream);
+  ix->times.scan_split = false;
 
   // --- queries: copy (never mutate caller buffer), cosine-normalize, norms
   if ((st = dbuf_reserve(ix->ws_queries, (size_t)nq * d * 4, ix->stream,
@@ -1581,9 +1627,15 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
   DbufGuard g_range(ws_range);
   int64_t* d_rcounts = nullptr;
   uint64_t* d_thr = nullptr;
-  auto build_thr = [&]() -> dg_status {
-    h_thr.resize(nq);
-    if (metric == DG_METRIC_L2) {
+  // with_thr = false: only the count/lims/cursor arrays (binary Flat)
+  auto build_thr = [&](bool with_thr = true) -> dg_status {
+    h_thr.resize(with_thr ? nq : 0);
+    if (!with_thr) {
+      // nothing to fill
+    } else if (is_bin) {  // key = the distance itself: no query norm, no sync
+      for (int64_t i = 0; i < nq; i++)
+        h_thr[i] = ((uint64_t)h_enc_f32(rr->radius) << 32);
+    } else if (metric == DG_METRIC_L2) {
       std::vector<float> h_qn(nq);
       DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
       DG_HIP_CHECK(hipMemcpy(h_qn.data(), dqn, (size_t)nq * 4,
@@ -1600,8 +1652,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     if (s2 != DG_OK) return s2;
     d_thr = (uint64_t*)ws_range.p;
     d_rcounts = (int64_t*)(d_thr + nq);
-    DG_HIP_CHECK(hipMemcpyAsync(d_thr, h_thr.data(), (size_t)nq * 8,
-                                hipMemcpyHostToDevice, ix->stream));
+    if (with_thr)
+      DG_HIP_CHECK(hipMemcpyAsync(d_thr, h_thr.data(), (size_t)nq * 8,
+                                  hipMemcpyHostToDevice, ix->stream));
     (void)hipMemsetAsync(d_rcounts, 0, (size_t)nq * 8, ix->stream);
     return DG_OK;
   };
@@ -1640,7 +1693,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
       return s2;
     }
     dgk::range_emit(ix->stream, d_packed, d_lims,
-                    (const int64_t*)ix->d_csr_ids.p, dqn, nq, metric,
+                    (const int64_t*)ix->d_csr_ids.p, dqn, nq, emit_metric,
                     metric == DG_METRIC_L2 ? 1 : 0, d_dist, d_ids64);
     float* h_dist = (float*)malloc(std::max<int64_t>(total, 1) * 4);
     int64_t* h_ids = (int64_t*)malloc(std::max<int64_t>(total, 1) * 8);
@@ -1659,14 +1712,15 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                              hipMemcpyDeviceToHost));
     }
     dbuf_free(d_res);
-    // per-query sort best-first (L2 asc / IP desc), ties toward smaller id
+    // per-query sort best-first (L2 and Hamming asc / IP desc), ties toward
+    // the smaller id
     for (int64_t qi = 0; qi < nq; qi++) {
       int64_t a = rr->lims[qi], b = rr->lims[qi + 1];
       std::vector<int64_t> ord(b - a);
       for (int64_t i = 0; i < b - a; i++) ord[i] = a + i;
       std::sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) {
         float dx = h_dist[x], dy = h_dist[y];
-        if (dx != dy) return metric == DG_METRIC_L2 ? dx < dy : dx > dy;
+        if (dx != dy) return emit_metric == DG_METRIC_L2 ? dx < dy : dx > dy;
         return h_ids[x] < h_ids[y];
       });
       std::vector<float> td(b - a);
@@ -1686,6 +1740,39 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
   if (!is_ivf) {
     // ---------- FLAT: chunked dots GEMM + dense select ----------
     const int64_t N = ix->ntotal;
+    if (rr && is_bin) {
+      // binary range search: two passes of the fused distance + radius
+      // kernel over the rows, no dists matrix (DESIGN.md §Binary indexes),
+      // so this sits ahead of the ws_dots / ws_topk reservations below
+      // (no per-query threshold either: the radius is a kernel argument)
+      if ((st = build_thr(false)) != DG_OK) return st;
+      if (!ix->capturing) (void)hipEventRecord(ix->ev[1], ix->stream);
+      if (!ix->capturing) (void)hipEventRecord(ix->ev[2], ix->stream);
+      const int32_t radius = (int32_t)rr->radius;
+      const uint32_t* rows = (const uint32_t*)ix->d_csr_codes.p;
+      (void)hipEventRecord(ix->ev[6], ix->stream);
+      const int64_t max_blocks = range_span_blocks();
+      dgk::hamming_range(ix->stream, false, (const uint32_t*)dq, nq, rows, N,
+                         d, d_bitmap, radius, d_rcounts, nullptr, nullptr,
+                         nullptr, max_blocks);
+      (void)hipEventRecord(ix->ev[7], ix->stream);
+      st = range_finish([&](const int64_t* d_lims, int64_t* d_cursors,
+                            uint64_t* d_out) -> dg_status {
+        (void)hipEventRecord(ix->ev[8], ix->stream);
+        dgk::hamming_range(ix->stream, true, (const uint32_t*)dq, nq, rows, N,
+                           d, d_bitmap, radius, nullptr, d_lims, d_cursors,
+                           d_out, max_blocks);
+        (void)hipEventRecord(ix->ev[9], ix->stream);
+        return DG_OK;
+      });
+      (void)hipEventRecord(ix->ev[3], ix->stream);
+      (void)hipEventRecord(ix->ev[4], ix->stream);
+      ix->times.scan_split = st == DG_OK;
+      ix->times.last_scan_bytes_alg =
+          2 * (int64_t)ix->ntotal * (ix->d_user / 8);  // two passes
+      ix->times.last_nq = nq;
+      return st;
+    }
     const int64_t max_dots = (int64_t)(2048ull << 20) / 4;  // 2 GiB of f32
     int64_t chunk_cols =
         std::max<int64_t>(65536, std::min<int64_t>(N, max_dots / nq));
@@ -1758,6 +1845,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           dbuf_free(d_off2);
           return s3;
         });
+      // dg_stats reads ev[0..4] once last_nq is set: leave none unrecorded
+      (void)hipEventRecord(ix->ev[3], ix->stream);
+      (void)hipEventRecord(ix->ev[4], ix->stream);
       ix->times.last_nq = nq;
       return st;
     }
@@ -2046,6 +2136,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           return DG_OK;
         });
       }
+      (void)hipEventRecord(ix->ev[4], ix->stream);  // as above, for dg_stats
       ix->times.last_nq = nq;
       return st;
     }
@@ -2299,7 +2390,8 @@ extern "C" dg_status dg_range_search(dg_index* ix, int64_t nq, const float* x,
     return DG_EINVAL;
   }
   if (ix->is_bin) {
-    dg_set_error("range search is not supported on binary indexes");
+    dg_set_error("dg_range_search called on a binary index: use "
+                 "dg_range_search_binary");
     return DG_ENOT_SUPPORT;
   }
   DeviceGuard g(ix->device);
@@ -2335,6 +2427,69 @@ extern "C" dg_status dg_range_search(dg_index* ix, int64_t nq, const float* x,
                      nullptr, &rr);
 }
 
+// Binary form: restates the same reference bodies instantiated over
+// faiss::IndexBinary (vector_index_flat.cc:304-308, vector_index_ivf_flat.cc:
+// 290-292,342-352): integer radius, a row is returned iff hamming < radius;
+// nprobe from the parameter (<= 0: 80, clamped to nlist; Flat ignores it).
+extern "C" dg_status dg_range_search_binary(dg_index* ix, int64_t nq,
+                                            const uint8_t* x, int32_t radius,
+                                            int32_t nprobe,
+                                            const dg_filter* filter,
+                                            int64_t* lims, int64_t** out_ids,
+                                            float** out_dists) {
+  if (out_ids) *out_ids = nullptr;  // always safe to hand to dg_free
+  if (out_dists) *out_dists = nullptr;
+  if (!ix || !x || !lims || !out_ids || !out_dists || nq <= 0) {
+    dg_set_error("bad range search args");
+    return DG_EINVAL;
+  }
+  if (!entry_matches(ix, true, "dg_range_search_binary")) return DG_EINVAL;
+  if (nq > kMaxScanLen) {
+    dg_set_error("nq %lld > %d per call unsupported", (long long)nq,
+                 kMaxScanLen);
+    return DG_EINVAL;
+  }
+  DeviceGuard g(ix->device);
+  // untrained IVF: blank result, OK (ivf_flat.cc:311-315); radius <= 0
+  // admits no distance
+  if (!ix->trained || ix->ntotal == 0 || radius <= 0) {
+    memset(lims, 0, ((size_t)nq + 1) * 8);
+    return DG_OK;
+  }
+  {
+    std::unique_lock lk(ix->rw, std::defer_lock);
+    if (!ix->csr_valid) {
+      lk.lock();
+      if (!ix->csr_valid) {
+        dg_status st = finalize_csr(ix);
+        if (st != DG_OK) return st;
+      }
+    }
+  }
+  std::shared_lock lk(ix->rw);
+  const size_t qbytes = (size_t)nq * (ix->d_user / 8);
+  dg_dbuf& t_in = g_tls_staging.for_device(ix->device).in;
+  dg_status st;
+  if ((st = dbuf_reserve(t_in, qbytes, ix->stream, false)) != DG_OK)
+    return st;
+  DG_HIP_CHECK(hipMemcpyAsync(t_in.p, x, qbytes, hipMemcpyHostToDevice,
+                              ix->stream));
+  // distances never exceed d: any larger radius admits every row, and the
+  // clamp keeps the f32 threshold exact
+  dg_range_req rr{(float)std::min(radius, ix->d_user + 1), lims, out_ids,
+                  out_dists};
+  std::lock_guard sg(ix->search_mu);
+  st = search_core(ix, nq, (const float*)t_in.p, 1, nprobe, filter, nullptr,
+                   nullptr, &rr);
+  if (st != DG_OK) {  // a failed call hands nothing back
+    free(*out_ids);
+    free(*out_dists);
+    *out_ids = nullptr;
+    *out_dists = nullptr;
+  }
+  return st;
+}
+
 extern "C" void dg_free(void* p) { free(p); }
 
 // ---------------- save / load (container v1) ----------------
@@ -2343,7 +2498,8 @@ static const uint32_t kMagic = 0x44474931;  // "DGI1"
 extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   if (!ix || !path) return DG_EINVAL;
   if (ix->is_bin) {
-    dg_set_error("save is not supported on binary indexes");
+    dg_set_error("container v1 does not hold binary indexes: use "
+                 "dg_save_faiss_binary");
     return DG_ENOT_SUPPORT;
   }
   std::shared_lock lk(ix->rw);
@@ -2604,6 +2760,12 @@ extern "C" dg_status dg_stats(dg_index* ix, dg_stats_out* out) {
     float ms01 = 0, ms23 = 0, ms04 = 0;
     (void)hipEventElapsedTime(&ms01, ix->ev[0], ix->ev[1]);
     (void)hipEventElapsedTime(&ms23, ix->ev[2], ix->ev[3]);
+    if (ix->times.scan_split) {  // count pass + compact pass
+      float a = 0, b = 0;
+      (void)hipEventElapsedTime(&a, ix->ev[6], ix->ev[7]);
+      (void)hipEventElapsedTime(&b, ix->ev[8], ix->ev[9]);
+      ms23 = a + b;
+    }
     (void)hipEventElapsedTime(&ms04, ix->ev[0], ix->ev[4]);
     out->last_coarse_ms = ms01;
     out->last_scan_ms = ms23;

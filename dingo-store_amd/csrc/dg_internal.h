@@ -49,6 +49,11 @@ dg_status dg_ingest_rows(dg_index* ix, int64_t n, const int64_t* ids,
                          const float* x, const uint8_t* codes,
                          const int32_t* assign);
 
+// The same for the binary kinds: rows of d/8 packed bytes (no word padding),
+// assign = null for Flat.
+dg_status dg_ingest_bits(dg_index* ix, int64_t n, const int64_t* ids,
+                         const uint8_t* bits, const int32_t* assign);
+
 // Device-side filter descriptor (POD copied into kernel args).
 struct dg_dev_filter {
   int32_t kind;    // dg_filter_kind
@@ -81,6 +86,9 @@ struct dg_stage_times {
   int64_t acc_scan_launches = 0;
   int64_t last_scan_bytes_alg = 0;
   int64_t last_nq = 0;
+  // binary Flat range search: the scan is two kernel passes with host work
+  // between them, timed as ev[6..7] + ev[8..9] instead of ev[2..3]
+  bool scan_split = false;
 };
 
 struct dg_index {
@@ -228,6 +236,17 @@ void tombstone(hipStream_t s, const int64_t* pos, int64_t n, int64_t* ids);
 void hamming_dists(hipStream_t s, const uint32_t* X, int64_t nq,
                    const uint32_t* Y, int64_t cols, int32_t wp, float* out,
                    int64_t ld);
+// Binary Flat range search, fused distance + radius test (no dists matrix).
+// compact = false adds each query's hit count to counts[nq] (lims, cursors,
+// out unused); compact = true appends pack(distance, row) for every hit at
+// out[lims[q] + ...] through the zeroed cursors[nq] (counts unused).  A hit
+// is a row whose bitmap bit is set (null bitmap: all) with distance < radius.
+// The columns are covered by as many launches as max_blocks requires.
+void hamming_range(hipStream_t s, bool compact, const uint32_t* X, int64_t nq,
+                   const uint32_t* Y, int64_t cols, int32_t wp,
+                   const uint32_t* bitmap, int32_t radius, int64_t* counts,
+                   const int64_t* lims, int64_t* cursors, uint64_t* out,
+                   int64_t max_blocks /* per launch, <= 2^30 */);
 // per-row argmin of a dense score matrix, ties toward the smaller column
 void argmin_score(hipStream_t s, const float* scores, int64_t n, int32_t cols,
                   int32_t* out);

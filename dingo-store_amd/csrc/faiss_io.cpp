@@ -59,8 +59,24 @@ struct FWriter {
 struct FReader {
   FILE* f = nullptr;
   bool ok = true;
+  // bytes not yet consumed; ~0 = unknown (no bound applied)
+  uint64_t left = ~(uint64_t)0;
   void raw(void* p, size_t n) {
     if (ok && fread(p, 1, n, f) != n) ok = false;
+    if (left != ~(uint64_t)0) left = n <= left ? left - n : 0;
+  }
+  // learn the file size so that counts read from the file can be bounded
+  // by the bytes that are actually there before anything is resized
+  void measure() {
+    long pos = ftell(f);
+    if (pos < 0 || fseek(f, 0, SEEK_END) != 0) return;
+    long end = ftell(f);
+    if (end >= pos) left = (uint64_t)(end - pos);
+    fseek(f, pos, SEEK_SET);
+  }
+  // count elements of elem bytes each still fit in the file
+  bool fits(uint64_t count, uint64_t elem) const {
+    return ok && (elem == 0 || count <= left / elem);
   }
   uint8_t u8() { uint8_t v = 0; raw(&v, 1); return v; }
   int32_t i32() { int32_t v = 0; raw(&v, 4); return v; }
@@ -130,6 +146,7 @@ void write_direct_map(FWriter& w) {
 bool read_direct_map(FReader& r) {
   uint8_t type = r.u8();
   uint64_t n = r.u64();
+  if (!r.fits(n, 8)) return false;
   if (type == 0 || type == 1) {
     // NoMap stores an empty array; Array stores ntotal entries
     std::vector<int64_t> skip(n);
@@ -233,20 +250,24 @@ struct InvLists {
   std::vector<std::vector<int64_t>> ids;
 };
 
-bool read_invlists(FReader& r, InvLists& il) {
+// want_nlist: the nlist the index header stated.  Everything below is
+// sized by it, so it has to match before anything is allocated.
+bool read_invlists(FReader& r, InvLists& il, uint64_t want_nlist) {
   if (r.u32() != fcc("ilar")) return false;
   il.nlist = r.u64();
   il.code_size = r.u64();
-  if (!r.ok || il.nlist > (1u << 24) || il.code_size > (1u << 20))
+  if (!r.ok || il.nlist != want_nlist || il.nlist > (1u << 24) ||
+      il.code_size > (1u << 20))
     return false;
   uint32_t lt = r.u32();
   std::vector<uint64_t> sizes(il.nlist, 0);
   if (lt == fcc("full")) {
     uint64_t cnt = r.u64();
-    if (cnt != il.nlist) return false;
+    if (cnt != il.nlist || !r.fits(cnt, 8)) return false;
     r.raw(sizes.data(), il.nlist * 8);
   } else if (lt == fcc("sprs")) {
     uint64_t cnt = r.u64();  // count of u64s: pairs of (idx, size)
+    if (!r.fits(cnt, 8)) return false;
     std::vector<uint64_t> pairs(cnt);
     r.raw(pairs.data(), cnt * 8);
     for (uint64_t j = 0; j + 1 < cnt; j += 2) {
@@ -262,6 +283,7 @@ bool read_invlists(FReader& r, InvLists& il) {
   for (uint64_t l = 0; l < il.nlist; l++) {
     uint64_t n = sizes[l];
     if (!n) continue;
+    if (!r.fits(n, il.code_size + 8)) return false;
     il.codes[l].resize(n * il.code_size);
     il.ids[l].resize(n);
     r.raw(il.codes[l].data(), il.codes[l].size());
@@ -287,7 +309,8 @@ struct DeviceGuard {
 extern "C" dg_status dg_save_faiss(dg_index* ix, const char* path) {
   if (!ix || !path) return DG_EINVAL;
   if (ix->is_bin) {
-    dg_set_error("faiss save is not supported on binary indexes");
+    dg_set_error("dg_save_faiss called on a binary index: use "
+                 "dg_save_faiss_binary");
     return DG_ENOT_SUPPORT;
   }
   std::shared_lock lk(ix->rw);
@@ -499,8 +522,7 @@ static dg_status load_faiss_impl(dg_index** out, const char* path,
         desc.kind = DG_INDEX_IVF_FLAT;
       }
       InvLists il;
-      if (!read_invlists(r, il)) break;
-      if (il.nlist != nlist) break;
+      if (!read_invlists(r, il, nlist)) break;
       size_t want_cs = h4 == fcc("IwPQ") ? (size_t)M : (size_t)oh.d * 4;
       if (il.code_size != want_cs) break;
       if ((st = dg_index_create(&ix, &desc)) != DG_OK) break;
@@ -545,4 +567,317 @@ static dg_status load_faiss_impl(dg_index** out, const char* path,
   }
   *out = ix;
   return DG_OK;
+}
+
+// ---------------- binary (Hamming) containers ----------------
+// faiss 1.7.x write_index_binary layout for the two shapes the reference
+// constructs over faiss::IndexBinary (vector_index_flat.cc:99-102,
+// vector_index_ivf_flat.cc:75-80):
+//   binary header: d:i32, code_size:i32 (= d/8), ntotal:i64, is_trained:u8,
+//                  metric_type:i32 (= 1) — 21 bytes, no dummy fields
+//   IndexBinaryFlat    "IBxF" header, xb vector<u8> (ntotal * code_size)
+//   IndexBinaryIDMap2  "IBM2" ("IBMp" = IDMap) header, inner index, id_map
+//   IndexBinaryIVF     "IBwF" header, nlist:u64, nprobe:u64, quantizer
+//                      (IBxF holding the centroids), direct map, inverted
+//                      lists as in the float IVF ("ilar", code_size = d/8)
+namespace {
+
+constexpr int32_t kBinMaxNlist = 1023 * 256 - 1;  // scan-length cap, dg_abi
+
+void write_binary_header(FWriter& w, int32_t d, int64_t ntotal, bool trained) {
+  w.i32(d);
+  w.i32(d / 8);
+  w.i64(ntotal);
+  w.u8(trained ? 1 : 0);
+  w.i32(1);  // METRIC_L2: what faiss::IndexBinary carries
+}
+
+void write_binary_flat(FWriter& w, int32_t d, int64_t n, const uint8_t* xb) {
+  w.u32(fcc("IBxF"));
+  write_binary_header(w, d, n, true);
+  w.u64((uint64_t)n * (d / 8));
+  if (n) w.raw(xb, (size_t)n * (d / 8));
+}
+
+struct BinHeader {
+  int32_t d = 0, code_size = 0, metric = 0;
+  int64_t ntotal = 0;
+  bool trained = false;
+};
+
+// DG_OK, DG_EIO (malformed) or DG_ENOT_SUPPORT (a metric other than L2,
+// which the reference rejects too, vector_index_flat.cc:433-438, or an
+// untrained index)
+dg_status read_binary_header(FReader& r, BinHeader& h) {
+  h.d = r.i32();
+  h.code_size = r.i32();
+  h.ntotal = r.i64();
+  h.trained = r.u8() != 0;
+  h.metric = r.i32();
+  if (!r.ok) return DG_EIO;
+  if (h.d < 8 || h.d > 32768 || h.d % 8 != 0 || h.code_size != h.d / 8 ||
+      h.ntotal < 0)
+    return DG_EIO;
+  if (h.metric != 1) {
+    dg_set_error("binary faiss container with metric_type %d unsupported "
+                 "(only METRIC_L2 = 1)", h.metric);
+    return DG_ENOT_SUPPORT;
+  }
+  if (!h.trained) {
+    // the writer refuses an untrained index and the reference refuses to
+    // load one (vector_index_flat.cc:408-410)
+    dg_set_error("binary faiss container with is_trained = 0 unsupported");
+    return DG_ENOT_SUPPORT;
+  }
+  return DG_OK;
+}
+
+dg_status unsupported_fourcc(uint32_t h4) {
+  dg_set_error("unsupported binary faiss index fourcc 0x%08x '%c%c%c%c'", h4,
+               (h4 & 0x7f) >= 32 ? (int)(h4 & 0x7f) : '?',
+               ((h4 >> 8) & 0x7f) >= 32 ? (int)((h4 >> 8) & 0x7f) : '?',
+               ((h4 >> 16) & 0x7f) >= 32 ? (int)((h4 >> 16) & 0x7f) : '?',
+               ((h4 >> 24) & 0x7f) >= 32 ? (int)((h4 >> 24) & 0x7f) : '?');
+  return DG_ENOT_SUPPORT;
+}
+
+// "IBxF" index whose dimension must equal d
+dg_status read_binary_flat(FReader& r, int32_t d, BinHeader& h,
+                           std::vector<uint8_t>& xb) {
+  uint32_t h4 = r.u32();
+  if (!r.ok) return DG_EIO;
+  if (h4 != fcc("IBxF")) return unsupported_fourcc(h4);
+  dg_status st = read_binary_header(r, h);
+  if (st != DG_OK) return st;
+  if (h.d != d) return DG_EIO;
+  uint64_t count = r.u64();
+  if (!r.ok || !r.fits(count, 1) ||
+      !r.fits((uint64_t)h.ntotal, (uint64_t)h.code_size) ||
+      count != (uint64_t)h.ntotal * (uint64_t)h.code_size)
+    return DG_EIO;
+  xb.resize(count);
+  if (count) r.raw(xb.data(), count);
+  return r.ok ? DG_OK : DG_EIO;
+}
+
+// negative ids are reserved (a negative stored id marks a removed row)
+bool ids_valid(const std::vector<int64_t>& ids) {
+  for (int64_t id : ids)
+    if (id < 0) return false;
+  return true;
+}
+
+// everything a binary container holds, parsed on the host
+struct BinFile {
+  int32_t kind = 0, d = 0, nlist = 0;
+  std::vector<uint8_t> cents;   // IVF: nlist x d/8
+  std::vector<int64_t> ids;     // file order
+  std::vector<uint8_t> rows;    // ids.size() x d/8
+  std::vector<int32_t> assign;  // IVF: list of every row
+};
+
+dg_status parse_binary(FReader& r, BinFile& bf) {
+  uint32_t h4 = r.u32();
+  if (!r.ok) return DG_EIO;
+  dg_status st;
+  if (h4 == fcc("IBM2") || h4 == fcc("IBMp")) {
+    BinHeader oh, ih;
+    if ((st = read_binary_header(r, oh)) != DG_OK) return st;
+    if ((st = read_binary_flat(r, oh.d, ih, bf.rows)) != DG_OK) return st;
+    uint64_t nmap = r.u64();
+    if (!r.ok || !r.fits(nmap, 8) || nmap != (uint64_t)ih.ntotal ||
+        oh.ntotal != ih.ntotal)
+      return DG_EIO;
+    bf.ids.resize(nmap);
+    if (nmap) r.raw(bf.ids.data(), nmap * 8);
+    if (!r.ok || !ids_valid(bf.ids)) return DG_EIO;
+    bf.kind = DG_INDEX_BINARY_FLAT;
+    bf.d = oh.d;
+    return DG_OK;
+  }
+  if (h4 == fcc("IBwF")) {
+    BinHeader oh, qh;
+    if ((st = read_binary_header(r, oh)) != DG_OK) return st;
+    uint64_t nlist = r.u64();
+    (void)r.u64();  // nprobe member (per-search in the reference)
+    if (!r.ok || nlist == 0 || nlist > (uint64_t)kBinMaxNlist) return DG_EIO;
+    if ((st = read_binary_flat(r, oh.d, qh, bf.cents)) != DG_OK) return st;
+    if ((uint64_t)qh.ntotal != nlist) return DG_EIO;
+    if (!read_direct_map(r)) return DG_EIO;
+    InvLists il;
+    if (!read_invlists(r, il, nlist)) return DG_EIO;  // nlist <= the cap
+    if (il.code_size != (uint64_t)oh.code_size) return DG_EIO;
+    int64_t total = 0;
+    for (uint64_t l = 0; l < nlist; l++) {
+      const size_t n = il.ids[l].size();
+      if (!n) continue;
+      total += (int64_t)n;
+      bf.ids.insert(bf.ids.end(), il.ids[l].begin(), il.ids[l].end());
+      bf.rows.insert(bf.rows.end(), il.codes[l].begin(), il.codes[l].end());
+      bf.assign.insert(bf.assign.end(), n, (int32_t)l);
+    }
+    if (total != oh.ntotal || !ids_valid(bf.ids)) return DG_EIO;
+    bf.kind = DG_INDEX_BINARY_IVF_FLAT;
+    bf.d = oh.d;
+    bf.nlist = (int32_t)nlist;
+    return DG_OK;
+  }
+  return unsupported_fourcc(h4);
+}
+
+dg_status load_faiss_binary_impl(dg_index** out, const char* path,
+                                 int32_t device) {
+  if (!out || !path) return DG_EINVAL;
+  *out = nullptr;
+  FILE* f = fopen(path, "rb");
+  if (!f) {
+    dg_set_error("cannot open %s", path);
+    return DG_EIO;
+  }
+  // the whole file is read and checked on the host before the first device
+  // call: a malformed container is answered without a GPU
+  BinFile bf;
+  dg_status st;
+  {
+    FReader r{f};
+    r.measure();
+    try {
+      st = parse_binary(r, bf);
+    } catch (...) {
+      fclose(f);
+      throw;
+    }
+  }
+  fclose(f);
+  if (st != DG_OK) {
+    if (st == DG_EIO) dg_set_error("malformed binary faiss container %s", path);
+    return st;
+  }
+  dg_index_desc desc{};
+  desc.kind = bf.kind;
+  desc.metric = DG_METRIC_HAMMING;
+  desc.d = bf.d;
+  desc.nlist = bf.nlist;
+  desc.device = device;
+  desc.reserve = (int64_t)bf.ids.size();
+  dg_index* ix = nullptr;
+  if ((st = dg_index_create(&ix, &desc)) != DG_OK) return st;
+  if (bf.kind == DG_INDEX_BINARY_IVF_FLAT)
+    st = dg_set_centroids_binary(ix, bf.nlist, bf.cents.data());
+  // rows keep the list the file puts them in (no re-assignment)
+  if (st == DG_OK && !bf.ids.empty())
+    st = dg_ingest_bits(ix, (int64_t)bf.ids.size(), bf.ids.data(),
+                        bf.rows.data(),
+                        bf.assign.empty() ? nullptr : bf.assign.data());
+  if (st != DG_OK) {
+    dg_index_destroy(ix);
+    return st;
+  }
+  *out = ix;
+  return DG_OK;
+}
+
+}  // namespace
+
+extern "C" dg_status dg_save_faiss_binary(dg_index* ix, const char* path) {
+  if (!ix || !path) return DG_EINVAL;
+  if (!ix->is_bin) {
+    dg_set_error("dg_save_faiss_binary called on a float index (kind %d): "
+                 "use dg_save_faiss", ix->desc.kind);
+    return DG_EINVAL;
+  }
+  std::shared_lock lk(ix->rw);
+  DeviceGuard g{ix->device};
+  const int32_t d = ix->d_user;
+  const size_t cs = (size_t)d / 8;  // file row = d/8 bytes, word pad stripped
+  const bool is_flat = ix->desc.kind == DG_INDEX_BINARY_FLAT;
+  if (!is_flat && !ix->trained) {
+    dg_set_error("faiss save of untrained IVF index unsupported");
+    return DG_ENOT_SUPPORT;
+  }
+  const int64_t n = ix->ntotal;
+  HostRows h;  // codes = packed rows, arrival order
+  h.ids.resize(n);
+  h.assign.resize(n);
+  h.codes.resize((size_t)n * cs);
+  if (n) {
+    if (hipMemcpy(h.ids.data(), ix->d_ids.p, (size_t)n * 8,
+                  hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(h.assign.data(), ix->d_assign.p, (size_t)n * 4,
+                  hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy2D(h.codes.data(), cs, ix->d_codes.p, (size_t)ix->b_wp * 4,
+                    cs, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
+      dg_set_error("row download failed");
+      return DG_EINTERNAL;
+    }
+  }
+  std::vector<uint8_t> cents;
+  if (!is_flat) {
+    cents.resize((size_t)ix->desc.nlist * cs);
+    if (hipMemcpy2D(cents.data(), cs, ix->d_centroids.p, (size_t)ix->b_wp * 4,
+                    cs, (size_t)ix->desc.nlist,
+                    hipMemcpyDeviceToHost) != hipSuccess) {
+      dg_set_error("centroid download failed");
+      return DG_EINTERNAL;
+    }
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) {
+    dg_set_error("cannot open %s", path);
+    return DG_EIO;
+  }
+  FWriter w{f};
+  if (is_flat) {
+    // IndexBinaryIDMap2 { IndexBinaryFlat }: kept rows in arrival order
+    std::vector<uint8_t> kept;
+    std::vector<int64_t> idmap;
+    kept.reserve(h.codes.size());
+    for (int64_t i = 0; i < n; i++) {
+      if (h.ids[i] < 0) continue;  // tombstone
+      kept.insert(kept.end(), h.codes.begin() + (size_t)i * cs,
+                  h.codes.begin() + (size_t)(i + 1) * cs);
+      idmap.push_back(h.ids[i]);
+    }
+    const int64_t nk = (int64_t)idmap.size();
+    w.u32(fcc("IBM2"));
+    write_binary_header(w, d, nk, true);
+    write_binary_flat(w, d, nk, kept.data());
+    w.u64((uint64_t)nk);
+    if (nk) w.raw(idmap.data(), (size_t)nk * 8);
+  } else {
+    const int32_t nlist = ix->desc.nlist;
+    std::vector<std::vector<int64_t>> lists;
+    int64_t kept = 0;
+    group_rows(h, nlist, lists, &kept);
+    w.u32(fcc("IBwF"));
+    write_binary_header(w, d, kept, true);
+    w.u64((uint64_t)nlist);
+    w.u64(1);  // nprobe member default (searches pass their own)
+    write_binary_flat(w, d, nlist, cents.data());
+    write_direct_map(w);
+    // rows are byte codes of cs bytes held in h.codes, which is what
+    // write_invlists' "PQ" form copies: is_pq = true, M = bytes per row
+    write_invlists(w, h, lists, cs, d, /*is_pq=*/true, /*M=*/(int32_t)cs);
+  }
+  bool ok = w.ok;
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) {
+    dg_set_error("write failed for %s", path);
+    return DG_EIO;
+  }
+  return DG_OK;
+}
+
+extern "C" dg_status dg_load_faiss_binary(dg_index** out, const char* path,
+                                          int32_t device) {
+  // exception wall, as dg_load_faiss
+  try {
+    return load_faiss_binary_impl(out, path, device);
+  } catch (const std::exception& e) {
+    dg_set_error("binary faiss container load failed: %s", e.what());
+    return DG_EIO;
+  } catch (...) {
+    dg_set_error("binary faiss container load failed");
+    return DG_EIO;
+  }
 }

@@ -2329,16 +2329,14 @@ __global__ void k_scan_block_i64(const int64_t* in, int64_t n, int64_t* out,
 // assignment can exceed the 65535 limit of gridDim.y).
 static constexpr int kHamQ = 32;
 static constexpr int kHamW = 32;
-__global__ void __launch_bounds__(256) k_hamming_dists(
+// acc[j] = popcount(X[q0 + j] ^ Y[c0 + tid]) for the block's 256 columns and
+// kHamQ queries; rows and queries past the end read as zero words.  Shared
+// by k_hamming_dists and k_hamming_range.
+__device__ __forceinline__ void hamming_tile_acc(
     const uint32_t* __restrict__ X, int64_t nq, const uint32_t* __restrict__ Y,
-    int64_t cols, int32_t wp, uint32_t nx, float* __restrict__ out,
-    int64_t ld) {
-  __shared__ uint32_t ly[256 * (kHamW + 1)];
-  __shared__ __attribute__((aligned(16))) uint32_t lx[kHamW * kHamQ];
+    int64_t cols, int32_t wp, int64_t c0, int64_t q0, uint32_t* ly,
+    uint32_t* lx, int32_t (&acc)[kHamQ]) {
   const int tid = threadIdx.x;
-  const int64_t c0 = (int64_t)(blockIdx.x % nx) * 256;
-  const int64_t q0 = (int64_t)(blockIdx.x / nx) * kHamQ;
-  int32_t acc[kHamQ];
 #pragma unroll
   for (int j = 0; j < kHamQ; j++) acc[j] = 0;
   for (int32_t w0 = 0; w0 < wp; w0 += kHamW) {
@@ -2370,10 +2368,86 @@ __global__ void __launch_bounds__(256) k_hamming_dists(
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(256) k_hamming_dists(
+    const uint32_t* __restrict__ X, int64_t nq, const uint32_t* __restrict__ Y,
+    int64_t cols, int32_t wp, uint32_t nx, float* __restrict__ out,
+    int64_t ld) {
+  __shared__ uint32_t ly[256 * (kHamW + 1)];
+  __shared__ __attribute__((aligned(16))) uint32_t lx[kHamW * kHamQ];
+  const int tid = threadIdx.x;
+  const int64_t c0 = (int64_t)(blockIdx.x % nx) * 256;
+  const int64_t q0 = (int64_t)(blockIdx.x / nx) * kHamQ;
+  int32_t acc[kHamQ];
+  hamming_tile_acc(X, nq, Y, cols, wp, c0, q0, ly, lx, acc);
   if (c0 + tid >= cols) return;
 #pragma unroll
   for (int j = 0; j < kHamQ; j++)
     if (q0 + j < nq) out[(q0 + j) * ld + c0 + tid] = (float)acc[j];
+}
+
+// Binary Flat range search: the distance tile of k_hamming_dists with the
+// radius test fused in, so no nq x N matrix is written or read back.  Run
+// twice over the same inputs: the COUNT pass adds each query's hits to
+// counts[q] (ballot popcount per wave, the four waves summed through LDS,
+// one atomic per (block, query) with hits), the host turns counts into
+// lims, and the COMPACT pass appends pack_cand(distance, row) behind
+// lims[q] with one cursor atomic per (wave, query) that has hits.  A hit
+// is: column in range, pass-bitmap bit set (bitmap indexed by col_base +
+// column; null = every row passes), distance < radius.  Every lane takes
+// part in every ballot; lanes past cols carry hit = false.  The order of a
+// query's results is arbitrary (the host sorts them).
+template <bool COMPACT>
+__global__ void __launch_bounds__(256) k_hamming_range(
+    const uint32_t* __restrict__ X, int64_t nq, const uint32_t* __restrict__ Y,
+    int64_t cols, int32_t wp, uint32_t nx, int64_t col_base,
+    const uint32_t* __restrict__ bitmap, int32_t radius,
+    int64_t* __restrict__ counts, const int64_t* __restrict__ lims,
+    int64_t* __restrict__ cursors, uint64_t* __restrict__ out) {
+  __shared__ uint32_t ly[256 * (kHamW + 1)];
+  __shared__ __attribute__((aligned(16))) uint32_t lx[kHamW * kHamQ];
+  __shared__ int32_t lcnt[4][kHamQ];
+  const int tid = threadIdx.x;
+  const int lane = tid % WAVE, wave = tid / WAVE;
+  const int64_t c0 = (int64_t)(blockIdx.x % nx) * 256;
+  const int64_t q0 = (int64_t)(blockIdx.x / nx) * kHamQ;
+  int32_t acc[kHamQ];
+  hamming_tile_acc(X, nq, Y, cols, wp, c0, q0, ly, lx, acc);
+  const int64_t row = col_base + c0 + tid;
+  const bool ok = c0 + tid < cols &&
+                  (!bitmap || ((bitmap[row >> 5] >> (row & 31)) & 1));
+  if (!COMPACT) {
+#pragma unroll
+    for (int j = 0; j < kHamQ; j++) {
+      const uint64_t b = __ballot(ok && acc[j] < radius);
+      if (lane == 0) lcnt[wave][j] = __popcll(b);
+    }
+    __syncthreads();
+    if (tid < kHamQ && q0 + tid < nq) {
+      const int32_t c =
+          lcnt[0][tid] + lcnt[1][tid] + lcnt[2][tid] + lcnt[3][tid];
+      if (c)
+        atomicAdd((unsigned long long*)&counts[q0 + tid],
+                  (unsigned long long)c);
+    }
+  } else {
+    const uint64_t below = (1ull << lane) - 1;
+#pragma unroll
+    for (int j = 0; j < kHamQ; j++) {
+      const bool hit = ok && q0 + j < nq && acc[j] < radius;
+      const uint64_t b = __ballot(hit);
+      if (!b) continue;  // wave-uniform
+      long long base = 0;
+      if (lane == 0)
+        base = (long long)atomicAdd((unsigned long long*)&cursors[q0 + j],
+                                    (unsigned long long)__popcll(b));
+      base = __shfl(base, 0, WAVE);
+      if (hit)
+        out[lims[q0 + j] + base + __popcll(b & below)] =
+            pack_cand((float)acc[j], (uint32_t)row);
+    }
+  }
 }
 
 // argmin over a dense score row, key = score as is; tie: smaller column
@@ -3065,6 +3139,31 @@ void hamming_dists(hipStream_t s, const uint32_t* X, int64_t nq,
   const int64_t nx = ceil_div(cols, 256), ny = ceil_div(nq, kHamQ);
   hipLaunchKernelGGL(k_hamming_dists, dim3((uint32_t)(nx * ny)), dim3(256), 0,
                      s, X, nq, Y, cols, wp, (uint32_t)nx, out, ld);
+}
+
+void hamming_range(hipStream_t s, bool compact, const uint32_t* X, int64_t nq,
+                   const uint32_t* Y, int64_t cols, int32_t wp,
+                   const uint32_t* bitmap, int32_t radius, int64_t* counts,
+                   const int64_t* lims, int64_t* cursors, uint64_t* out,
+                   int64_t max_blocks) {
+  if (!nq || !cols) return;
+  const int64_t ny = ceil_div(nq, kHamQ);
+  // column spans keep the 1-D grid at max_blocks (at least one column tile)
+  const int64_t tiles = max_blocks / ny;
+  const int64_t span = (tiles > 0 ? tiles : 1) * 256;
+  for (int64_t cb = 0; cb < cols; cb += span) {
+    const int64_t cc = cols - cb < span ? cols - cb : span;
+    const int64_t nx = ceil_div(cc, 256);
+    const uint32_t* Yc = Y + (size_t)cb * wp;
+    if (compact)
+      hipLaunchKernelGGL(k_hamming_range<true>, dim3((uint32_t)(nx * ny)),
+                         dim3(256), 0, s, X, nq, Yc, cc, wp, (uint32_t)nx, cb,
+                         bitmap, radius, counts, lims, cursors, out);
+    else
+      hipLaunchKernelGGL(k_hamming_range<false>, dim3((uint32_t)(nx * ny)),
+                         dim3(256), 0, s, X, nq, Yc, cc, wp, (uint32_t)nx, cb,
+                         bitmap, radius, counts, lims, cursors, out);
+  }
 }
 
 void argmin_score(hipStream_t s, const float* scores, int64_t n, int32_t cols,

@@ -105,6 +105,15 @@ def _load():
         C.POINTER(_Filter), C.c_void_p, C.c_void_p,
     ]
     lib.dg_mirror_selftest_binary.restype = C.c_int
+    lib.dg_range_search_binary.argtypes = [
+        C.c_void_p, C.c_int64, _u8p, C.c_int32, C.c_int32,
+        C.POINTER(_Filter), _i64p, C.POINTER(C.POINTER(C.c_int64)),
+        C.POINTER(C.POINTER(C.c_float)),
+    ]
+    lib.dg_save_faiss_binary.argtypes = [C.c_void_p, C.c_char_p]
+    lib.dg_load_faiss_binary.argtypes = [C.POINTER(C.c_void_p), C.c_char_p,
+                                         C.c_int32]
+    lib.dg_free.argtypes = [C.c_void_p]
     return lib
 
 
@@ -352,6 +361,34 @@ class Index:
         l.dg_free(C.cast(out_dists, C.c_void_p))
         return lims, dists, ids
 
+    def range_search_binary(self, queries_u8, radius, nprobe=0, filt=None):
+        """Binary radius search: rows with hamming(query, row) < radius
+        (an integer).  Returns (lims[nq+1], dists, ids), per query ascending
+        by (distance, id); dists are the integer distances as float32."""
+        q = np.ascontiguousarray(queries_u8, np.uint8)
+        nq = q.shape[0]
+        lims = np.zeros(nq + 1, np.int64)
+        out_ids = C.POINTER(C.c_int64)()
+        out_dists = C.POINTER(C.c_float)()
+        l = lib()
+        fp = C.byref(filt) if filt is not None else None
+        st = l.dg_range_search_binary(self.h, nq, q, int(radius), nprobe, fp,
+                                      lims, C.byref(out_ids),
+                                      C.byref(out_dists))
+        try:
+            _check(st, "dg_range_search_binary")
+            total = int(lims[-1])
+            if total:
+                dists = np.ctypeslib.as_array(out_dists, (total,)).copy()
+                ids = np.ctypeslib.as_array(out_ids, (total,)).copy()
+            else:
+                dists = np.empty(0, np.float32)
+                ids = np.empty(0, np.int64)
+        finally:
+            l.dg_free(C.cast(out_ids, C.c_void_p))
+            l.dg_free(C.cast(out_dists, C.c_void_p))
+        return lims, dists, ids
+
     def sync(self):
         _check(lib().dg_sync(self.h), "dg_sync")
 
@@ -390,6 +427,20 @@ class Index:
         h = C.c_void_p()
         _check(l.dg_load_faiss(C.byref(h), path.encode(), metric, device),
                "dg_load_faiss")
+        return cls._from_handle(h)
+
+    def save_faiss_binary(self, path):
+        """Write the binary index as a faiss write_index_binary container
+        (IndexBinaryIDMap2{IndexBinaryFlat} or IndexBinaryIVF)."""
+        _check(lib().dg_save_faiss_binary(self.h, path.encode()),
+               "dg_save_faiss_binary")
+
+    @classmethod
+    def load_faiss_binary(cls, path, device=-1):
+        """Load a binary faiss container (IBM2/IBMp{IBxF} or IBwF)."""
+        h = C.c_void_p()
+        _check(lib().dg_load_faiss_binary(C.byref(h), path.encode(), device),
+               "dg_load_faiss_binary")
         return cls._from_handle(h)
 
     @classmethod

@@ -9,10 +9,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 #include <algorithm>
 #include <queue>
 #include <unordered_set>
+
+#include <unistd.h>
 
 namespace dingogpu {
 
@@ -109,6 +112,9 @@ class GpuIndexBase : public VectorIndex {
     desc.pq_nbits = 8;
     desc.device = device;
     create_st_ = dg_index_create(&idx_, &desc);
+    dg_stats_out s{};
+    if (create_st_ == DG_OK && dg_stats(idx_, &s) == DG_OK)
+      nlist_created_ = s.nlist;  // after the defaults of dg_index_create
   }
   ~GpuIndexBase() override {
     if (idx_) dg_index_destroy(idx_);
@@ -226,17 +232,32 @@ class GpuIndexBase : public VectorIndex {
   void LockWrite() override { dg_lock_write(idx_); }
   void UnlockWrite() override { dg_unlock_write(idx_); }
   Status Save(const std::string& path) override {
-    if (binary_) return {kEVectorNotSupport, "binary index save"};
+    if (binary_) return from_dg(dg_save_faiss_binary(idx_, path.c_str()));
     // the snapshot cycle ships faiss::write_index files
     // (vector_index_snapshot_manager.cc:583-599) — emit the compatible
     // container so CPU nodes can ingest the snapshot
     return from_dg(dg_save_faiss(idx_, path.c_str()));
   }
   Status Load(const std::string& path) override {
-    if (binary_) return {kEVectorNotSupport, "binary index load"};
     dg_index* ni = nullptr;
-    dg_status st = dg_load_faiss(&ni, path.c_str(), (int32_t)metric_, -1);
+    dg_status st =
+        binary_ ? dg_load_faiss_binary(&ni, path.c_str(), -1)
+                : dg_load_faiss(&ni, path.c_str(), (int32_t)metric_, -1);
     if (st != DG_OK) return from_dg(st);
+    if (binary_) {
+      // the file must hold this index's kind and dimension (the reference's
+      // dynamic_cast and "dimension not match", vector_index_flat.cc:389-406)
+      dg_stats_out now{}, got{};
+      // and, for IVF, its current or its configured nlist
+      // (vector_index_ivf_flat.cc:495-498)
+      if (dg_stats(idx_, &now) != DG_OK || dg_stats(ni, &got) != DG_OK ||
+          got.kind != now.kind || got.d != dim_ ||
+          (got.kind == DG_INDEX_BINARY_IVF_FLAT && got.nlist != now.nlist &&
+           got.nlist != nlist_created_)) {
+        dg_index_destroy(ni);
+        return {kEInternal, "loaded index kind, dimension or nlist not match"};
+      }
+    }
     dg_index_destroy(idx_);
     idx_ = ni;
     return Status::OK();
@@ -304,17 +325,18 @@ class GpuIndexBase : public VectorIndex {
 
   Status RangeSearch(const std::vector<VectorWithId>& queries, float radius,
                      const std::vector<std::shared_ptr<FilterFunctor>>& fs,
-                     bool, const VectorSearchParameter&,
+                     bool, const VectorSearchParameter& p,
                      std::vector<VectorWithDistanceResult>& results) override {
     // mirrors VectorIndexIvfFlat::RangeSearch: for IP/cosine the dingo
     // radius converts to a faiss score threshold 1 - r
     // (src/vector/vector_index_ivf_flat.cc:302-305)
-    if (binary_) return {kEVectorNotSupport, "binary index range search"};
     if (queries.empty())
       return {kEillegalParamteters, "vector_with_ids is empty"};
     std::vector<float> x;
+    std::vector<uint8_t> xb;
     std::vector<int64_t> ids;
-    Status s = pack(queries, dim_, x, ids);
+    Status s = binary_ ? pack_bits(queries, dim_, xb, ids)
+                       : pack(queries, dim_, x, ids);
     if (!s.ok()) return s;
     dg_filter df{};
     dg_filter* dfp = nullptr;
@@ -326,8 +348,15 @@ class GpuIndexBase : public VectorIndex {
     std::vector<int64_t> lims(queries.size() + 1);
     int64_t* rids = nullptr;
     float* rdists = nullptr;
-    dg_status st = dg_range_search(idx_, (int64_t)queries.size(), x.data(),
-                                   r, dfp, lims.data(), &rids, &rdists);
+    // binary: the reference hands its float radius to faiss's int parameter
+    // (vector_index_flat.cc:304-308), i.e. truncates; distances pass through
+    dg_status st =
+        binary_ ? dg_range_search_binary(idx_, (int64_t)queries.size(),
+                                         xb.data(), (int32_t)radius,
+                                         p.binary_ivf_flat_nprobe, dfp,
+                                         lims.data(), &rids, &rdists)
+                : dg_range_search(idx_, (int64_t)queries.size(), x.data(), r,
+                                  dfp, lims.data(), &rids, &rdists);
     if (st != DG_OK) return from_dg(st);
     results.clear();
     results.resize(queries.size());
@@ -337,8 +366,10 @@ class GpuIndexBase : public VectorIndex {
         vd.vector_with_id.id = rids[i];
         vd.vector_with_id.vector.dimension = dim_;
         vd.metric_type = metric_;
-        vd.distance = (metric_ == MetricType::kL2) ? rdists[i]
-                                                   : 1.0f - rdists[i];
+        vd.distance = (metric_ == MetricType::kL2 ||
+                       metric_ == MetricType::kHamming)
+                          ? rdists[i]
+                          : 1.0f - rdists[i];
         results[q].vector_with_distances.push_back(std::move(vd));
       }
     }
@@ -355,6 +386,7 @@ class GpuIndexBase : public VectorIndex {
   MetricType metric_;
   int32_t dim_;
   bool binary_ = false;
+  int32_t nlist_created_ = 0;  // nlist_org_ of the reference
   int64_t train_data_size_ = 0;
 };
 
@@ -396,7 +428,6 @@ class GpuBinaryFlatIndex : public GpuIndexBase {
   GpuBinaryFlatIndex(int32_t d, int dev)
       : GpuIndexBase(DG_INDEX_BINARY_FLAT, MetricType::kHamming, d, 0, dev) {}
   bool NeedTrain() override { return false; }
-  bool SupportSave() override { return false; }
 };
 
 class GpuBinaryIvfFlatIndex : public GpuIndexBase {
@@ -405,7 +436,6 @@ class GpuBinaryIvfFlatIndex : public GpuIndexBase {
       : GpuIndexBase(DG_INDEX_BINARY_IVF_FLAT, MetricType::kHamming, d, nlist,
                      dev) {}
   bool NeedTrain() override { return !IsTrained(); }
-  bool SupportSave() override { return false; }
 };
 
 class GpuIvfPqIndex : public GpuIndexBase {
@@ -884,17 +914,75 @@ extern "C" int dg_mirror_selftest_binary(void) {
     if (res[0].vector_with_distances.empty() ||
         res[0].vector_with_distances[0].vector_with_id.id != batch[5].id)
       return 123;
-    // out of scope for the binary kinds
+    // range search against the hamming lambda: every row strictly below
+    // the radius, ascending, with its distance passed through
+    int64_t live = 0;
+    if (!idx->GetCount(live).ok() || live != n) return 124;
     std::vector<VectorWithDistanceResult> rr;
-    if (idx->RangeSearch(queries, 10.f, {}, false, p, rr).code !=
-        kEVectorNotSupport)
-      return 124;
-    if (idx->Save("/tmp/dg_mirror_selftest_binary.idx").code !=
-        kEVectorNotSupport)
-      return 125;
-    if (idx->Load("/tmp/dg_mirror_selftest_binary.idx").code !=
-        kEVectorNotSupport)
+    const float radius = 85.9f;  // truncates to 85
+    if (!idx->RangeSearch(queries, radius, {}, false, p, rr).ok()) return 124;
+    if (rr.size() != queries.size()) return 124;
+    for (size_t i = 0; i < queries.size(); i++) {
+      auto& r = rr[i].vector_with_distances;
+      size_t want = 0;
+      for (int j = 0; j < n; j++)
+        if (hamming(queries[i], batch[j]) < 85) want++;
+      if (r.size() != want || want == 0) return 124;
+      for (size_t j = 0; j < r.size(); j++) {
+        const int64_t row = (r[j].vector_with_id.id - 1) / 3;
+        if (row < 0 || row >= n) return 124;
+        if (r[j].distance != (float)hamming(queries[i], batch[row]) ||
+            r[j].distance >= 85.f)
+          return 124;
+        if (j && r[j].distance < r[j - 1].distance) return 124;
+        if (r[j].metric_type != MetricType::kHamming) return 124;
+      }
+    }
+    // Save -> Load into a fresh index -> the same top-4
+    if (!idx->SupportSave()) return 125;
+    const std::string path = "/tmp/dg_mirror_selftest_binary." +
+                             std::to_string((long)getpid()) + "." +
+                             std::to_string(kind) + ".idx";
+    std::vector<VectorWithDistanceResult> before, after;
+    if (!idx->Search(queries, 4, {}, false, p, before).ok()) return 125;
+    if (!idx->Save(path).ok()) return 125;
+    auto fresh =
+        kind == 0 ? NewBinaryFlatIndex(d) : NewBinaryIvfFlatIndex(d, 8);
+    Status ls = fresh ? fresh->Load(path) : Status{kEInternal, "create"};
+    // a file of the other kind, or of another dimension, is refused
+    auto other =
+        kind == 0 ? NewBinaryIvfFlatIndex(d, 8) : NewBinaryFlatIndex(d);
+    auto wide = kind == 0 ? NewBinaryFlatIndex(d + 8)
+                          : NewBinaryIvfFlatIndex(d + 8, 8);
+    bool refused = other && wide && !other->Load(path).ok() &&
+                   !wide->Load(path).ok();
+    if (kind == 1) {  // an IVF file of another nlist
+      auto more = NewBinaryIvfFlatIndex(d, 16);
+      refused = refused && more && !more->Load(path).ok();
+    }
+    remove(path.c_str());
+    if (!ls.ok() || !refused) return 126;
+    int64_t cnt2 = 0;
+    if (!fresh->GetCount(cnt2).ok() || cnt2 != n || !fresh->IsTrained())
       return 126;
+    if (!fresh->Search(queries, 4, {}, false, p, after).ok()) return 126;
+    if (after.size() != before.size()) return 126;
+    for (size_t i = 0; i < before.size(); i++) {
+      auto& a = before[i].vector_with_distances;
+      auto& b = after[i].vector_with_distances;
+      if (a.size() != b.size()) return 126;
+      // equal distances; ids equal wherever the distance is not tied (the
+      // row order inside a list may differ after a reload)
+      for (size_t j = 0; j < a.size(); j++) {
+        if (a[j].distance != b[j].distance) return 126;
+        const bool tied =
+            (j && a[j - 1].distance == a[j].distance) ||
+            (j + 1 < a.size() && a[j + 1].distance == a[j].distance) ||
+            j + 1 == a.size();
+        if (!tied && a[j].vector_with_id.id != b[j].vector_with_id.id)
+          return 126;
+      }
+    }
   }
   return 0;
 }

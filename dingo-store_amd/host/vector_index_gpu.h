@@ -235,8 +235,11 @@ std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
 
 // Binary (Hamming) indexes: dim in bits, vectors carry binary_values of
 // dim / 8 bytes; distances are the integer Hamming distance, passed through
-// (vector_index_utils.cc:640-650).  RangeSearch, Save and Load return
-// kEVectorNotSupport.
+// (vector_index_utils.cc:640-650).  RangeSearch truncates its float radius
+// to faiss's int (a row is returned iff hamming < radius) and reads nprobe
+// from binary_ivf_flat_nprobe; Save/Load speak the faiss write_index_binary
+// container, and Load refuses a file of another kind or dimension, or (IVF)
+// of an nlist that is neither the index's current nor its configured one.
 std::unique_ptr<VectorIndex> NewBinaryFlatIndex(int32_t dim, int device = -1);
 std::unique_ptr<VectorIndex> NewBinaryIvfFlatIndex(int32_t dim,
                                                    int32_t ncentroids,
@@ -250,6 +253,7 @@ extern "C" {
 // IP/cosine, vector_index_utils.cc:634; self-top-1).  Returns 0 on success.
 int dg_mirror_selftest(void);
 // Same for the binary indexes: Flat and IVF-Flat through the mirror, self
-// top-1 at distance 0 and the Hamming distance passed through unflipped.
+// top-1 at distance 0 and the Hamming distance passed through unflipped,
+// range search against a host popcount, Save -> Load -> the same top-4.
 int dg_mirror_selftest_binary(void);
 }

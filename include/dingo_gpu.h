@@ -268,7 +268,8 @@ dg_status dg_load_faiss(dg_index** out, const char* path,
  * dg_index_destroy work unchanged.  The float entry points return
  * DG_EINVAL on a binary index and these return DG_EINVAL on a float one;
  * dg_range_search, dg_save and dg_save_faiss return DG_ENOT_SUPPORT on a
- * binary index. */
+ * binary index (range search and the faiss container have the _binary
+ * calls below; the own container v1 does not hold binary indexes). */
 dg_status dg_train_binary(dg_index* idx, int64_t n, const uint8_t* x);
 dg_status dg_set_centroids_binary(dg_index* idx, int32_t nlist,
                                   const uint8_t* centroids);
@@ -286,6 +287,42 @@ dg_status dg_search_binary_device(dg_index* idx, int64_t nq,
                                   const uint8_t* d_x, int32_t k,
                                   int32_t nprobe, const dg_filter* filter,
                                   float* d_out_dist, int64_t* d_out_ids);
+
+/* Binary range search (VectorIndexFlat/IvfFlat::RangeSearch over
+ * faiss::IndexBinary, vector_index_flat.cc:304-308,
+ * vector_index_ivf_flat.cc:290-292,342-352).  radius is an integer, as in
+ * faiss::IndexBinary::range_search: a row is returned iff hamming(query,
+ * row) < radius, so radius <= 0 returns nothing and radius > d every
+ * admissible row (not removed, passing the filter, and for IVF in a probed
+ * list: nprobe <= 0 => 80, clamped to nlist, list mask applied; Flat
+ * ignores nprobe).  An untrained IVF index returns all-zero lims and DG_OK.
+ * CSR results like dg_range_search: within a query ascending by (distance,
+ * id), out_dists the exact integer distance as float32.  *out_ids and
+ * *out_dists are set on every return (possibly to NULL) and may always be
+ * handed to dg_free.  nq is limited to 261887 per call. */
+dg_status dg_range_search_binary(dg_index* idx, int64_t nq, const uint8_t* x,
+                                 int32_t radius, int32_t nprobe,
+                                 const dg_filter* filter,
+                                 int64_t* lims /* nq+1 */, int64_t** out_ids,
+                                 float** out_dists);
+/* Binary faiss containers (faiss::write_index_binary 1.7.x layout, the
+ * snapshot files of the binary kinds: vector_index_flat.cc:355-356,380-381,
+ * vector_index_ivf_flat.cc:399-400,424-425):
+ *   BINARY_FLAT     -> IndexBinaryIDMap2{IndexBinaryFlat}  ("IBM2"/"IBxF")
+ *   BINARY_IVF_FLAT -> IndexBinaryIVF, IndexBinaryFlat quantizer ("IBwF")
+ * Save drops tombstoned rows; Flat rows keep arrival order, IVF rows are
+ * grouped by list in arrival order; an untrained IVF index answers
+ * DG_ENOT_SUPPORT.  Load also accepts "IBMp" and sparse ("sprs") list
+ * sizes, keeps every IVF row in the list the file puts it in, answers
+ * DG_ENOT_SUPPORT for any other fourcc (named in dg_last_error; every float
+ * container is one), for a metric other than METRIC_L2
+ * (vector_index_flat.cc:433-438) and for is_trained = 0, and DG_EIO for
+ * malformed content.  The
+ * file is read and checked completely before the first device call.  Byte
+ * layout in DESIGN.md. */
+dg_status dg_save_faiss_binary(dg_index* idx, const char* path);
+dg_status dg_load_faiss_binary(dg_index** out, const char* path,
+                               int32_t device);
 
 /* ---- multi-GPU sharding support ----
  * Each rank holds a shard of the database (row-sharded)

@@ -19,6 +19,17 @@ one step, and the achieved (query, row) pairs/s against the VALU bound of
 clock given with --clock-mhz.
 
   python tools/bench_binary.py --shapes flat,ivf,baseline --out result.json
+
+--range R replaces the shapes with one measurement of binary Flat range
+search (1M x 768 bits, batch 256, radius R; uniform random rows give about
+10 hits per query at R = 326): per step the wall time of
+dg_range_search_binary, the device time of the two k_hamming_range passes
+together (hipEvents on the index stream, from dg_stats) and their
+difference, the host-side remainder (two synchronizes, copies, sort).  The
+same index then runs the top-k search of the flat shape, so the scan time
+with the distance-matrix round trip stands beside it.
+
+  python tools/bench_binary.py --range 326 --out range.json
 """
 import argparse
 import json
@@ -105,6 +116,50 @@ def run_flat(torch, a):
     return out
 
 
+def run_range(torch, a):
+    d, n, nq, k = 768, a.flat_rows, 256, 10
+    base = gen_bits(torch, n, d // 8, a.seed)
+    q = gen_bits(torch, nq, d // 8, a.seed + 1)
+    idx = dg.Index(dg.BINARY_FLAT, dg.HAMMING, d)
+    idx.add(np.arange(n, dtype=np.int64), base.cpu().numpy())
+    qh = q.cpu().numpy()
+    wall, dev = [], []
+    for i in range(a.warmup + a.steps):
+        t0 = time.perf_counter()
+        lims, dist, _ = idx.range_search_binary(qh, a.range)
+        ms = (time.perf_counter() - t0) * 1e3
+        if i >= a.warmup:
+            wall.append(ms)
+            dev.append(idx.stats()["last_scan_ms"])
+    wall, dev = np.array(wall), np.array(dev)
+    rest = wall - dev
+    # the same resident index through the top-k path (dists matrix + select)
+    ms, st, tk_dist, _ = time_steps(torch, idx, q, k, 0, a.steps, a.warmup)
+    out = {
+        "shape": "binary_flat_range", "batch": nq, "rows": n, "d_bits": d,
+        "radius": a.range, "steps": a.steps, "warmup": a.warmup,
+        "hits_total": int(lims[-1]), "hits_per_query": float(lims[-1]) / nq,
+        "dist_checksum": float(dist.astype(np.float64).sum()),
+        "range_call_ms_median": float(np.median(wall)),
+        "range_call_ms_min": float(wall.min()),
+        "range_call_ms_max": float(wall.max()),
+        "range_kernels_ms_median": float(np.median(dev)),
+        "range_kernels_ms_min": float(dev.min()),
+        "range_kernels_ms_max": float(dev.max()),
+        "range_host_rest_ms_median": float(np.median(rest)),
+        "range_host_rest_ms_min": float(rest.min()),
+        "range_host_rest_ms_max": float(rest.max()),
+        "topk_k": k,
+        "topk_step_ms_median": float(np.median(ms)),
+        "topk_step_ms_min": float(ms.min()),
+        "topk_step_ms_max": float(ms.max()),
+        "topk_scan_ms_stats": st["last_scan_ms"],
+        "topk_dist_checksum": float(tk_dist.double().sum()),
+    }
+    idx.close()
+    return out
+
+
 def run_baseline(torch, a):
     d, n, nq, k = 768, a.flat_rows, 256, 10
     base = gen_bits(torch, n, d // 8, a.seed)
@@ -165,6 +220,9 @@ def main():
                     help="engine clock for the VALU bound; 0 = read it "
                          "after each shape's timed steps, 2400 if it "
                          "cannot be read")
+    ap.add_argument("--range", type=int, default=0, metavar="R",
+                    help="measure binary Flat range search at radius R "
+                         "instead of the --shapes")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.steps < 20:
@@ -174,7 +232,11 @@ def main():
     runners = {"flat": run_flat, "ivf": run_ivf, "baseline": run_baseline}
     results = []
     fixed_clock = a.clock_mhz
-    for name in a.shapes.split(","):
+    if a.range > 0:
+        results.append(run_range(torch, a))
+        print(json.dumps(results[0]), flush=True)
+        a.shapes = ""
+    for name in filter(None, a.shapes.split(",")):
         a.clock_mhz, a.clock_source = fixed_clock, "argument"
         if not fixed_clock:
             # read right after a warm run of the same shape would be ideal;
