@@ -291,6 +291,19 @@ extern "C" int32_t dg_ivfpq_max_m(int32_t device) {
   return (int32_t)(dgk::max_launch_lds() / per_m) & ~3;  // m % 4 == 0
 }
 
+// nbits = 4 (k_ivfpq4_scan): the packed code tile, the list's f16 S table
+// and one f32 lookup table per wave; m % 8 == 0 (whole-dword code rows)
+extern "C" int32_t dg_ivfpq_max_m_nbits(int32_t device, int32_t nbits) {
+  if (nbits == 8) return dg_ivfpq_max_m(device);
+  if (nbits != 4 || device < 0 || device >= dg_device_count()) return 0;
+  DeviceGuard g(device);
+  const size_t lds = dgk::max_launch_lds();
+  int32_t m = (int32_t)(lds / dgk::ivfpq4_scan_lds(8) * 8);  // first guess
+  while (m > 0 && dgk::ivfpq4_scan_lds(m) > lds) m -= 8;
+  while (dgk::ivfpq4_scan_lds(m + 8) <= lds) m += 8;
+  return m;
+}
+
 extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   if (!out || !dp) {
     dg_set_error("null arg");
@@ -331,14 +344,21 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   if (desc.kind == DG_INDEX_IVF_PQ) {
     if (desc.pq_m <= 0) desc.pq_m = 64;      // kCreateIvfPqParamNsubvector
     if (desc.pq_nbits <= 0) desc.pq_nbits = 8;  // kCreateIvfPqParamNbitsPerIdx
-    if (desc.pq_nbits != 8) {
-      dg_set_error("only nbits=8 supported (reference default, constant.h)");
+    if (desc.pq_nbits != 8 && desc.pq_nbits != 4) {
+      dg_set_error("IVF-PQ nbits=%d unsupported: the supported set is "
+                   "{4, 8} (8 is the reference default, constant.h)",
+                   desc.pq_nbits);
       return DG_ENOT_SUPPORT;
     }
     if (d_user % 4 != 0 || d_user % desc.pq_m != 0 || desc.pq_m % 4 != 0) {
       dg_set_error(
           "IVF-PQ needs d %% 4 == 0, d %% m == 0 and m %% 4 == 0 "
           "(d=%d m=%d)", d_user, desc.pq_m);
+      return DG_ENOT_SUPPORT;
+    }
+    if (desc.pq_nbits == 4 && desc.pq_m % 8 != 0) {
+      dg_set_error("IVF-PQ nbits=4 needs m %% 8 == 0, a packed code row of "
+                   "whole dwords (m=%d)", desc.pq_m);
       return DG_ENOT_SUPPORT;
     }
   }
@@ -356,12 +376,16 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   if (desc.kind == DG_INDEX_IVF_PQ) {
     // the scan stages a code tile and the list's f16 S table in LDS; an m
     // whose default tile cannot be launched has no scan at all
-    const int32_t max_m = dg_ivfpq_max_m(desc.device >= 0 ? desc.device : 0);
+    const int32_t max_m = dg_ivfpq_max_m_nbits(
+        desc.device >= 0 ? desc.device : 0, desc.pq_nbits);
     if (desc.pq_m > max_m) {
       dg_set_error("IVF-PQ m=%d unsupported: the scan needs %zu bytes of LDS "
                    "per block, this device launches m <= %d",
                    desc.pq_m,
-                   dgk::ivfpq_scan_lds(dgk::kPqTileRows, desc.pq_m), max_m);
+                   desc.pq_nbits == 4
+                       ? dgk::ivfpq4_scan_lds(desc.pq_m)
+                       : dgk::ivfpq_scan_lds(dgk::kPqTileRows, desc.pq_m),
+                   max_m);
       return DG_ENOT_SUPPORT;
     }
   }
@@ -392,7 +416,8 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
         dbuf_reserve(ix->d_assign, (size_t)desc.reserve * 4, ix->stream,
                      false) == DG_OK;
     if (ok && desc.kind == DG_INDEX_IVF_PQ)
-      ok = dbuf_reserve(ix->d_codes, (size_t)desc.reserve * desc.pq_m,
+      ok = dbuf_reserve(ix->d_codes,
+                        (size_t)desc.reserve * dg_pq_code_size(desc),
                         ix->stream, false) == DG_OK;
     if (ok && is_bin)
       ok = dbuf_reserve(ix->d_codes, (size_t)desc.reserve * ix->b_wp * 4,
@@ -712,10 +737,11 @@ static dg_status finish_pq_tables(dg_index* ix) {
   const int32_t d = ix->desc.d;
   const int32_t dsub = d / M;
   const int32_t nlist = ix->desc.nlist;
+  const int32_t ksub = dg_pq_ksub(ix->desc);
   dg_status st;
-  if ((st = dbuf_reserve(ix->d_S, (size_t)nlist * M * 256 * 2, ix->stream,
+  if ((st = dbuf_reserve(ix->d_S, (size_t)nlist * M * ksub * 2, ix->stream,
                          false)) != DG_OK ||
-      (st = dbuf_reserve(ix->d_cb_norms, (size_t)M * 256 * 4, ix->stream,
+      (st = dbuf_reserve(ix->d_cb_norms, (size_t)M * ksub * 4, ix->stream,
                          false)) != DG_OK)
     return st;
   // S is stored as f16: an entry above 65504 would become inf and turn
@@ -726,10 +752,10 @@ static dg_status finish_pq_tables(dg_index* ix) {
   if ((st = dbuf_reserve(d_flag, 4, ix->stream, false)) != DG_OK) return st;
   DG_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, ix->stream));
   dgk::build_S(ix->stream, (const float*)ix->d_centroids.p,
-               (const float*)ix->d_codebooks.p, nlist, M, dsub, d,
+               (const float*)ix->d_codebooks.p, nlist, M, ksub, dsub, d,
                (__half*)ix->d_S.p, (int32_t*)d_flag.p);
   dgk::row_norms(ix->stream, (const float*)ix->d_codebooks.p,
-                 (int64_t)M * 256, dsub, (float*)ix->d_cb_norms.p);
+                 (int64_t)M * ksub, dsub, (float*)ix->d_cb_norms.p);
   int32_t overflow = 0;
   DG_HIP_CHECK(hipMemcpyAsync(&overflow, d_flag.p, 4, hipMemcpyDeviceToHost,
                               ix->stream));
@@ -748,7 +774,8 @@ static dg_status finish_pq_tables(dg_index* ix) {
 extern "C" dg_status dg_set_codebooks(dg_index* ix, int32_t m, int32_t nbits,
                                       const float* codebooks) {
   if (!ix || !codebooks) return DG_EINVAL;
-  if (ix->desc.kind != DG_INDEX_IVF_PQ || m != ix->desc.pq_m || nbits != 8) {
+  if (ix->desc.kind != DG_INDEX_IVF_PQ || m != ix->desc.pq_m ||
+      nbits != ix->desc.pq_nbits) {
     dg_set_error("codebook shape mismatch (m=%d nbits=%d)", m, nbits);
     return DG_EINVAL;
   }
@@ -759,7 +786,7 @@ extern "C" dg_status dg_set_codebooks(dg_index* ix, int32_t m, int32_t nbits,
   }
   DeviceGuard g(ix->device);
   const int32_t dsub = ix->desc.d / m;
-  size_t bytes = (size_t)m * 256 * dsub * 4;
+  size_t bytes = (size_t)m * dg_pq_ksub(ix->desc) * dsub * 4;
   dg_status st = dbuf_reserve(ix->d_codebooks, bytes, ix->stream, false);
   if (st != DG_OK) return st;
   DG_HIP_CHECK(hipMemcpyAsync(ix->d_codebooks.p, codebooks, bytes,
@@ -783,8 +810,21 @@ extern "C" dg_status dg_get_codebooks(dg_index* ix, float* out) {
   DeviceGuard g(ix->device);
   const int32_t dsub = ix->desc.d / ix->desc.pq_m;
   DG_HIP_CHECK(hipMemcpy(out, ix->d_codebooks.p,
-                         (size_t)ix->desc.pq_m * 256 * dsub * 4,
+                         (size_t)ix->desc.pq_m * dg_pq_ksub(ix->desc) * dsub *
+                             4,
                          hipMemcpyDeviceToHost));
+  return DG_OK;
+}
+
+extern "C" dg_status dg_pq_params(dg_index* ix, int32_t* m,
+                                  int32_t* nbits) {
+  if (!ix || !m || !nbits) return DG_EINVAL;
+  if (ix->desc.kind != DG_INDEX_IVF_PQ) {
+    dg_set_error("not an IVF-PQ index");
+    return DG_EINVAL;
+  }
+  *m = ix->desc.pq_m;
+  *nbits = ix->desc.pq_nbits;
   return DG_OK;
 }
 
@@ -826,10 +866,11 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
 
     if (ix->desc.kind == DG_INDEX_IVF_PQ) {
       // PQ encoder training (faiss IndexIVFPQ::train_encoder restated):
-      // per-subspace 256-centroid L2 k-means over coarse residuals of the
-      // train set (kmeans_device subsamples to 256*256 internally).
+      // per-subspace ksub-centroid L2 k-means over coarse residuals of the
+      // train set (kmeans_device subsamples to 256*ksub internally).
       const int32_t M = ix->desc.pq_m;
       const int32_t dsub = d / M;
+      const int32_t ksub = dg_pq_ksub(ix->desc);
       dg_dbuf d_asg{}, d_res{}, d_sub{};
       if ((st = dbuf_reserve(d_asg, (size_t)n * 4, ix->stream, false)) !=
               DG_OK ||
@@ -838,7 +879,7 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
           (st = dbuf_reserve(d_sub, (size_t)n * dsub * 4, ix->stream,
                              false)) != DG_OK ||
           (st = dbuf_reserve(ix->d_codebooks,
-                             (size_t)M * 256 * dsub * 4, ix->stream,
+                             (size_t)M * ksub * dsub * 4, ix->stream,
                              false)) != DG_OK) {
         dbuf_free(d_asg);
         dbuf_free(d_res);
@@ -861,10 +902,10 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
             st = DG_EINTERNAL;
             break;
           }
-          st = kmeans_device(ix, (const float*)d_sub.p, n, dsub, 256,
+          st = kmeans_device(ix, (const float*)d_sub.p, n, dsub, ksub,
                              DG_METRIC_L2, seed,
                              (float*)ix->d_codebooks.p +
-                                 (size_t)m * 256 * dsub);
+                                 (size_t)m * ksub * dsub);
         }
       }
       dbuf_free(d_asg);
@@ -981,12 +1022,14 @@ static dg_status pq_encode(dg_index* ix, const float* d_x, int64_t n,
   const int32_t M = ix->desc.pq_m;
   const int32_t d = ix->desc.d;
   const int32_t dsub = d / M;
+  const int32_t ksub = dg_pq_ksub(ix->desc);
+  const int32_t cs = dg_pq_code_size(ix->desc);
   const int64_t CH = std::min<int64_t>(n, 1 << 20);
   dg_dbuf d_res{}, d_dots{}, d_amin{};
   dg_status st;
   if ((st = dbuf_reserve(d_res, (size_t)CH * d * 4, ix->stream, false)) !=
           DG_OK ||
-      (st = dbuf_reserve(d_dots, (size_t)CH * 256 * 4, ix->stream, false)) !=
+      (st = dbuf_reserve(d_dots, (size_t)CH * ksub * 4, ix->stream, false)) !=
           DG_OK ||
       (st = dbuf_reserve(d_amin, (size_t)CH * 4, ix->stream, false)) !=
           DG_OK) {
@@ -1003,19 +1046,21 @@ static dg_status pq_encode(dg_index* ix, const float* d_x, int64_t n,
     for (int32_t m = 0; m < M; m++) {
       if (rocblas_sgemm(
               ix->blas, rocblas_operation_transpose, rocblas_operation_none,
-              256, (rocblas_int)c, dsub, &one,
-              (const float*)ix->d_codebooks.p + (size_t)m * 256 * dsub, dsub,
+              ksub, (rocblas_int)c, dsub, &one,
+              (const float*)ix->d_codebooks.p + (size_t)m * ksub * dsub, dsub,
               (const float*)d_res.p + m * dsub, d, &zero, (float*)d_dots.p,
-              256) != rocblas_status_success) {
+              ksub) != rocblas_status_success) {
         dg_set_error("pq encode sgemm failed");
         st = DG_EINTERNAL;
         break;
       }
       dgk::argmin_rows(ix->stream, (const float*)d_dots.p,
-                       (const float*)ix->d_cb_norms.p + (size_t)m * 256, c,
-                       256, DG_METRIC_L2, (int32_t*)d_amin.p);
-      dgk::set_code(ix->stream, (const int32_t*)d_amin.p, c, m, M,
-                    d_codes_out + (size_t)s0 * M);
+                       (const float*)ix->d_cb_norms.p + (size_t)m * ksub, c,
+                       ksub, DG_METRIC_L2, (int32_t*)d_amin.p);
+      // 4-bit codes share bytes: the per-m launches are ordered on the one
+      // stream, so even m stores its byte and odd m ORs the high nibble in
+      dgk::set_code(ix->stream, (const int32_t*)d_amin.p, c, m, cs,
+                    ix->desc.pq_nbits, d_codes_out + (size_t)s0 * cs);
     }
   }
   dbuf_free(d_res);
@@ -1078,7 +1123,8 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   if (st == DG_OK)
     st = dbuf_reserve(ix->d_assign, (size_t)(n0 + n) * 4, ix->stream, true);
   if (st == DG_OK && is_pq)
-    st = dbuf_reserve(ix->d_codes, (size_t)(n0 + n) * ix->desc.pq_m,
+    st = dbuf_reserve(ix->d_codes,
+                      (size_t)(n0 + n) * dg_pq_code_size(ix->desc),
                       ix->stream, true);
   if (st == DG_OK && ix->is_bin)
     st = dbuf_reserve(ix->d_codes, (size_t)(n0 + n) * ix->b_wp * 4,
@@ -1130,7 +1176,8 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
     st = assign_rows(ix, dst, n, (int32_t*)ix->d_assign.p + n0);
     if (st == DG_OK && is_pq)
       st = pq_encode(ix, dst, n, (const int32_t*)ix->d_assign.p + n0,
-                     (uint8_t*)ix->d_codes.p + (size_t)n0 * ix->desc.pq_m);
+                     (uint8_t*)ix->d_codes.p +
+                         (size_t)n0 * dg_pq_code_size(ix->desc));
     if (st != DG_OK) {
       dbuf_free(staging);
       return st;
@@ -1175,7 +1222,8 @@ dg_status dg_ingest_rows(dg_index* ix, int64_t n, const int64_t* ids,
   if (st == DG_OK)
     st = dbuf_reserve(ix->d_assign, (size_t)(n0 + n) * 4, ix->stream, true);
   if (st == DG_OK && is_pq)
-    st = dbuf_reserve(ix->d_codes, (size_t)(n0 + n) * ix->desc.pq_m,
+    st = dbuf_reserve(ix->d_codes,
+                      (size_t)(n0 + n) * dg_pq_code_size(ix->desc),
                       ix->stream, true);
   if (st != DG_OK) return st;
   if (!is_pq) {
@@ -1184,8 +1232,9 @@ dg_status dg_ingest_rows(dg_index* ix, int64_t n, const int64_t* ids,
     if (st != DG_OK) return st;
   } else
     DG_HIP_CHECK(hipMemcpyAsync(
-        (uint8_t*)ix->d_codes.p + (size_t)n0 * ix->desc.pq_m, codes,
-        (size_t)n * ix->desc.pq_m, hipMemcpyHostToDevice, ix->stream));
+        (uint8_t*)ix->d_codes.p + (size_t)n0 * dg_pq_code_size(ix->desc),
+        codes, (size_t)n * dg_pq_code_size(ix->desc), hipMemcpyHostToDevice,
+        ix->stream));
   DG_HIP_CHECK(hipMemcpyAsync((int64_t*)ix->d_ids.p + n0, ids, (size_t)n * 8,
                               hipMemcpyHostToDevice, ix->stream));
   if (assign) {
@@ -1381,8 +1430,8 @@ static dg_status finalize_csr(dg_index* ix) {
     return st;
   }
   if (is_pq && (st = dbuf_reserve(ix->d_csr_codes,
-                                  (size_t)n * ix->desc.pq_m, ix->stream,
-                                  false)) != DG_OK)
+                                  (size_t)n * dg_pq_code_size(ix->desc),
+                                  ix->stream, false)) != DG_OK)
     return st;
   int32_t* d_counts = (int32_t*)ix->ws_small.p;
   uint32_t* d_perm = (uint32_t*)((char*)ix->ws_small.p + (size_t)nlist * 4);
@@ -1402,7 +1451,8 @@ static dg_status finalize_csr(dg_index* ix) {
                       d_counts, d_perm);
     if (is_pq) {
       dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_codes.p, d_perm, n,
-                        ix->desc.pq_m, (uint8_t*)ix->d_csr_codes.p);
+                        dg_pq_code_size(ix->desc),
+                        (uint8_t*)ix->d_csr_codes.p);
     } else if (is_bin) {  // word rows move as b_wp * 4 byte codes
       dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_codes.p, d_perm, n,
                         d * 4, (uint8_t*)rowmajor.p);
@@ -2031,7 +2081,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     const int32_t total_units = ix->total_chunks;
     // algorithmic bytes (roofline) summed on device, read back async into
     // pinned memory; dg_stats synchronizes on ev[5]
-    const int64_t row_bytes = is_pq    ? ix->desc.pq_m
+    const int64_t row_bytes = is_pq    ? dg_pq_code_size(ix->desc)
                               : is_bin ? (int64_t)(ix->d_user / 8)
                                        : (int64_t)(d * 4 + 4);
     if (ix->h_pinned && !ix->capturing) {
@@ -2054,25 +2104,26 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
       // subspace) then gather-scan codes
       const int32_t M = ix->desc.pq_m;
       const int32_t dsub = d / M;
-      if ((st = dbuf_reserve(ix->ws_T, (size_t)nq * M * 256 * 2, ix->stream,
+      const int32_t ksub = dg_pq_ksub(ix->desc);
+      if ((st = dbuf_reserve(ix->ws_T, (size_t)nq * M * ksub * 2, ix->stream,
                              false)) != DG_OK ||
-          (st = dbuf_reserve(ix->ws_Tf32, (size_t)nq * M * 256 * 4,
+          (st = dbuf_reserve(ix->ws_Tf32, (size_t)nq * M * ksub * 4,
                              ix->stream, false)) != DG_OK) {
         return st;
       }
       const float one = 1.0f, zero = 0.0f;
       if (rocblas_sgemm_strided_batched(
               ix->blas, rocblas_operation_transpose, rocblas_operation_none,
-              256, (rocblas_int)nq, dsub, &one,
-              (const float*)ix->d_codebooks.p, dsub, (int64_t)256 * dsub, dq,
+              ksub, (rocblas_int)nq, dsub, &one,
+              (const float*)ix->d_codebooks.p, dsub, (int64_t)ksub * dsub, dq,
               d, (int64_t)dsub, &zero, (float*)ix->ws_Tf32.p,
-              (rocblas_int)(M * 256), (int64_t)256,
+              (rocblas_int)(M * ksub), (int64_t)ksub,
               M) != rocblas_status_success) {
         dg_set_error("T build sgemm failed");
         return DG_EINTERNAL;
       }
       dgk::f32_to_f16(ix->stream, (const float*)ix->ws_Tf32.p,
-                      (int64_t)nq * M * 256, (__half*)ix->ws_T.p);
+                      (int64_t)nq * M * ksub, (__half*)ix->ws_T.p);
       // a scan that did not launch leaves ws_cand stale; never select on it
       DG_HIP_CHECK(dgk::ivfpq_scan(
           ix->stream, units, total_units,
@@ -2080,7 +2131,8 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           (const uint8_t*)ix->d_csr_codes.p, (const __half*)ix->d_S.p,
           (const __half*)ix->ws_T.p, (const float*)ix->ws_dots.p, nlist, M,
           inv_offsets32, inv_q, inv_rank, qp_off, q_cand_base, np, metric,
-          d_bitmap, chunk_rows, (uint64_t*)ix->ws_cand.p));
+          d_bitmap, chunk_rows, (uint64_t*)ix->ws_cand.p,
+          ix->desc.pq_nbits));
     } else {
       // THE scan (columnar v2)
       char* mp = (char*)ix->d_chunk_meta.p;
@@ -2530,7 +2582,8 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   }
   if (st == DG_OK && is_pq && ix->pq_trained) {
     const int32_t dsub = d / ix->desc.pq_m;
-    std::vector<float> cb((size_t)ix->desc.pq_m * 256 * dsub);
+    std::vector<float> cb((size_t)ix->desc.pq_m * dg_pq_ksub(ix->desc) *
+                          dsub);
     if (hipMemcpy(cb.data(), ix->d_codebooks.p, cb.size() * 4,
                   hipMemcpyDeviceToHost) != hipSuccess)
       st = DG_EINTERNAL;
@@ -2538,7 +2591,7 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   }
   if (st == DG_OK && ix->ntotal > 0) {
     const size_t CH = 1 << 20;  // rows per host staging chunk
-    const int32_t M = ix->desc.pq_m;
+    const int32_t M = dg_pq_code_size(ix->desc);  // code row bytes
     std::vector<float> vbuf(is_pq ? 0 : CH * ix->d_user);
     std::vector<uint8_t> cbuf(is_pq ? CH * M : 0);
     std::vector<int64_t> ibuf(CH);
@@ -2629,16 +2682,16 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
     }
     if (is_pq && trained) {
       const int32_t dsub = d / desc.pq_m;
-      std::vector<float> cb((size_t)desc.pq_m * 256 * dsub);
+      std::vector<float> cb((size_t)desc.pq_m * dg_pq_ksub(ix->desc) * dsub);
       if (fread(cb.data(), 4, cb.size(), f) != cb.size()) {
         st = DG_EIO;
         break;
       }
-      st = dg_set_codebooks(ix, desc.pq_m, 8, cb.data());
+      st = dg_set_codebooks(ix, desc.pq_m, ix->desc.pq_nbits, cb.data());
       if (st != DG_OK) break;
     }
     if (ntotal > 0) {
-      const int32_t M = desc.pq_m;
+      const int32_t M = dg_pq_code_size(ix->desc);  // code row bytes
       const int32_t dp = ix->desc.d;  // padded internal stride
       if ((st = dbuf_reserve(ix->d_ids, (size_t)ntotal * 8, ix->stream,
                              false)) != DG_OK ||

@@ -79,6 +79,16 @@ static inline bool dg_kind_is_flat(int32_t kind) {
   return kind == DG_INDEX_FLAT || kind == DG_INDEX_BINARY_FLAT;
 }
 
+// IVF-PQ geometry: codewords per subspace and bytes of one packed code row
+// (nbits = 8: one byte per sub-quantizer; nbits = 4: faiss's generic PQ
+// packing, sub-quantizer 2j in the low nibble of byte j, 2j+1 in the high)
+static inline int32_t dg_pq_ksub(const dg_index_desc& d) {
+  return 1 << d.pq_nbits;
+}
+static inline int32_t dg_pq_code_size(const dg_index_desc& d) {
+  return d.pq_m * d.pq_nbits / 8;
+}
+
 struct dg_stage_times {
   double coarse_ms = 0, scan_ms = 0, select_ms = 0, total_ms = 0;
   // cumulative since last reset (for bench averaging)
@@ -148,13 +158,14 @@ struct dg_index {
 
   // ---- IVF-PQ state ----
   bool pq_trained = false;
-  dg_dbuf d_codebooks;      // [M][256][dsub] f32
-  dg_dbuf d_codes;          // arrival [ntotal x M] u8 (raw vectors are NOT
-                            // kept for PQ; d_vectors stays empty)
-  dg_dbuf d_csr_codes;      // grouped [ntotal x M] u8
-  dg_dbuf d_S;              // [nlist][M][256] f16 ||c_m + cb||^2
-  dg_dbuf d_cb_norms;       // [M][256] f32 codebook entry norms (encode)
-  dg_dbuf ws_T;             // per-batch [nq][M][256] f16 q_sub . cb
+  // ksub = dg_pq_ksub (256 or 16), code_size = dg_pq_code_size (M or M/2)
+  dg_dbuf d_codebooks;      // [M][ksub][dsub] f32
+  dg_dbuf d_codes;          // arrival [ntotal x code_size] u8 (raw vectors
+                            // are NOT kept for PQ; d_vectors stays empty)
+  dg_dbuf d_csr_codes;      // grouped [ntotal x code_size] u8
+  dg_dbuf d_S;              // [nlist][M][ksub] f16 ||c_m + cb||^2
+  dg_dbuf d_cb_norms;       // [M][ksub] f32 codebook entry norms (encode)
+  dg_dbuf ws_T;             // per-batch [nq][M][ksub] f16 q_sub . cb
   dg_dbuf ws_Tf32;          // f32 GEMM output before f16 convert
 
   // optional list ownership mask (multi-GPU list sharding)
@@ -346,20 +357,28 @@ void compact_below_dense(hipStream_t s, const float* scores,
 // IVF-PQ
 void residual(hipStream_t s, const float* x, const int32_t* assign,
               const float* centroids, int64_t n, int32_t d, float* out);
+// writes sub-quantizer m of every row (code_size bytes per row).  nbits = 4
+// packs two per byte: even m stores the byte, odd m ORs its high nibble in,
+// so the per-m launches must be ordered (one stream) and ascend in m
 void set_code(hipStream_t s, const int32_t* amin, int64_t n, int32_t m,
-              int32_t M, uint8_t* codes);
+              int32_t code_size, int32_t nbits, uint8_t* codes);
+// M = bytes per row, a multiple of 4
 void gather_codes(hipStream_t s, const uint8_t* src, const uint32_t* perm,
                   int64_t n, int32_t M, uint8_t* dst);
 void build_S(hipStream_t s, const float* centroids, const float* codebooks,
-             int32_t nlist, int32_t M, int32_t dsub, int32_t d, __half* S,
+             int32_t nlist, int32_t M, int32_t ksub, int32_t dsub, int32_t d,
+             __half* S,
              int32_t* overflow);  // *overflow |= 1 if an entry exceeds f16
 // rows of the default k_ivfpq_scan tile (RPV=4 x 64 lanes)
 constexpr int32_t kPqTileRows = 256;
 size_t max_launch_lds();  // dynamic LDS per launch, current device
 size_t ivfpq_scan_lds(int32_t tile_rows, int32_t M);
+// LDS of one k_ivfpq4_scan block (nbits = 4, 256-row tiles)
+size_t ivfpq4_scan_lds(int32_t M);
 void f32_to_f16(hipStream_t s, const float* in, int64_t n, __half* out);
 // returns the launch status; no launch is issued if the tile's LDS does
-// not fit the device
+// not fit the device.  nbits = 8: csr_codes rows of M bytes, S and T rows of
+// 256 entries; nbits = 4: packed rows of M/2 bytes, 16-entry S and T rows
 hipError_t ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int64_t* csr_offsets, const uint8_t* csr_codes,
                       const __half* S, const __half* T,
@@ -368,7 +387,7 @@ hipError_t ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int32_t* inv_rank, const int64_t* qp_off,
                       const int64_t* q_cand_base, int32_t nprobe, int metric,
                       const uint32_t* bitmap, int32_t chunk_rows,
-                      uint64_t* cand);
+                      uint64_t* cand, int32_t nbits);
 // emit: resolve ids, apply metric convention
 void emit_results(hipStream_t s, const uint64_t* topk,
                   const int64_t* ids_lookup, const float* qnorms, int64_t nq,

@@ -6,7 +6,7 @@
 // three index shapes the reference constructs:
 //   FLAT     IndexIDMap2{IndexFlatL2|IndexFlatIP}  (vector_index_flat.cc:81-98)
 //   IVF_FLAT IndexIVFFlat                          (vector_index_ivf_flat.cc:805-823)
-//   IVF_PQ   IndexIVFPQ (by_residual, nbits=8)     (vector_index_raw_ivf_pq.cc:551-570)
+//   IVF_PQ   IndexIVFPQ (by_residual, nbits 8|4)    (vector_index_raw_ivf_pq.cc:551-570)
 //
 // Layout (faiss 1.7.x index_write.cpp / index_read.cpp, restated from the
 // published format — the reference's faiss fork is >= 1.7.3 since it uses
@@ -184,7 +184,7 @@ dg_status download_rows(dg_index* ix, HostRows& h) {
                 hipMemcpyDeviceToHost) != hipSuccess)
     return DG_EINTERNAL;
   if (is_pq) {
-    h.codes.resize((size_t)n * ix->desc.pq_m);
+    h.codes.resize((size_t)n * dg_pq_code_size(ix->desc));
     if (hipMemcpy(h.codes.data(), ix->d_codes.p, h.codes.size(),
                   hipMemcpyDeviceToHost) != hipSuccess)
       return DG_EINTERNAL;
@@ -373,20 +373,23 @@ extern "C" dg_status dg_save_faiss(dg_index* ix, const char* path) {
     if (is_pq) {
       const int32_t M = ix->desc.pq_m;
       const int32_t dsub = d / M;
-      std::vector<float> cb((size_t)M * 256 * dsub);
+      const int32_t nbits = ix->desc.pq_nbits;
+      const int32_t cs = dg_pq_code_size(ix->desc);
+      std::vector<float> cb((size_t)M * dg_pq_ksub(ix->desc) * dsub);
       if (hipMemcpy(cb.data(), ix->d_codebooks.p, cb.size() * 4,
                     hipMemcpyDeviceToHost) != hipSuccess) {
         fclose(f);
         return DG_EINTERNAL;
       }
       w.u8(1);          // by_residual (bool; faiss >= 1.7 writes 1 byte)
-      w.u64((uint64_t)M);  // code_size (M codes x 1 byte at nbits=8)
+      w.u64((uint64_t)cs);  // code_size = M * nbits / 8 (the device layout
+                            // is faiss's packing, so rows copy as they are)
       w.u64((uint64_t)d);  // ProductQuantizer.d
       w.u64((uint64_t)M);  // .M
-      w.u64(8);            // .nbits
+      w.u64((uint64_t)nbits);  // .nbits
       w.u64(cb.size());    // centroids vector<float>
       w.raw(cb.data(), cb.size() * 4);
-      write_invlists(w, h, lists, M, d, true, M);
+      write_invlists(w, h, lists, cs, d, true, cs);
     } else {
       write_invlists(w, h, lists, (size_t)d * 4, d, false, 0);
     }
@@ -500,11 +503,13 @@ static dg_status load_faiss_impl(dg_index** out, const char* path,
         uint64_t pq_d = r.u64();
         uint64_t pq_M = r.u64();
         uint64_t pq_nbits = r.u64();
-        if (!r.ok || pq_nbits != 8 || pq_d != (uint64_t)oh.d ||
-            pq_M != code_size || pq_M == 0 || oh.d % pq_M != 0) {
+        if (!r.ok || (pq_nbits != 8 && pq_nbits != 4) ||
+            pq_d != (uint64_t)oh.d || pq_M == 0 || pq_M > (uint64_t)oh.d ||
+            pq_M * pq_nbits != code_size * 8 || oh.d % pq_M != 0) {
           dg_set_error(
               "unsupported IwPQ parameters (code_size=%llu M=%llu nbits=%llu"
-              " — only byte codes with by_residual are supported)",
+              " — only nbits 4 or 8 with code_size = M*nbits/8 and "
+              "by_residual are supported)",
               (unsigned long long)code_size, (unsigned long long)pq_M,
               (unsigned long long)pq_nbits);
           st = DG_ENOT_SUPPORT;
@@ -512,9 +517,9 @@ static dg_status load_faiss_impl(dg_index** out, const char* path,
         }
         M = (int32_t)pq_M;
         desc.pq_m = M;
-        desc.pq_nbits = 8;
+        desc.pq_nbits = (int32_t)pq_nbits;
         uint64_t nc = r.u64();
-        if (!r.ok || nc != (uint64_t)M * 256 * (oh.d / M)) break;
+        if (!r.ok || nc != ((uint64_t)M << pq_nbits) * (oh.d / M)) break;
         cb.resize(nc);
         r.raw(cb.data(), nc * 4);
         if (!r.ok) break;
@@ -523,13 +528,14 @@ static dg_status load_faiss_impl(dg_index** out, const char* path,
       }
       InvLists il;
       if (!read_invlists(r, il, nlist)) break;
-      size_t want_cs = h4 == fcc("IwPQ") ? (size_t)M : (size_t)oh.d * 4;
+      size_t want_cs = h4 == fcc("IwPQ") ? (size_t)dg_pq_code_size(desc)
+                                         : (size_t)oh.d * 4;
       if (il.code_size != want_cs) break;
       if ((st = dg_index_create(&ix, &desc)) != DG_OK) break;
       if ((st = dg_set_centroids(ix, (int32_t)nlist, cents.data())) != DG_OK)
         break;
       if (h4 == fcc("IwPQ") &&
-          (st = dg_set_codebooks(ix, M, 8, cb.data())) != DG_OK)
+          (st = dg_set_codebooks(ix, M, desc.pq_nbits, cb.data())) != DG_OK)
         break;
       // flatten lists into arrival arrays with their file assignment
       std::vector<int64_t> ids;

@@ -525,6 +525,12 @@ __global__ void k_gather_rows_by_index(const float* __restrict__ src,
   int64_t i = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
   int lane = threadIdx.x % WAVE;
   if (i >= n) return;
+  if (d & 3) {  // PQ subspaces of dsub % 4 != 0: rows are not 16 B aligned
+    const float* s1 = src + (size_t)idx[i] * d;
+    float* t1 = dst + (size_t)i * d;
+    for (int j = lane; j < d; j += WAVE) t1[j] = s1[j];
+    return;
+  }
   const float4* s = (const float4*)(src + (size_t)idx[i] * d);
   float4* t = (float4*)(dst + (size_t)i * d);
   for (int j = lane; j < d / 4; j += WAVE) t[j] = s[j];
@@ -738,10 +744,22 @@ __global__ void k_residual(const float* __restrict__ x,
   for (int i = lane; i < d; i += WAVE) o[i] = v[i] - c[i];
 }
 
+// cs = bytes per code row.  nbits = 4 (faiss generic PQ packing): sub-
+// quantizer 2j is the low nibble of byte j and 2j+1 the high one; even m
+// stores the byte, odd m ORs into it, so the neighbour survives as long as
+// the launches run in ascending m on one stream (pq_encode does).
 __global__ void k_set_code(const int32_t* __restrict__ amin, int64_t n,
-                           int32_t m, int32_t M, uint8_t* __restrict__ codes) {
+                           int32_t m, int32_t cs, int32_t nbits,
+                           uint8_t* __restrict__ codes) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) codes[(size_t)i * M + m] = (uint8_t)amin[i];
+  if (i >= n) return;
+  if (nbits == 8) {
+    codes[(size_t)i * cs + m] = (uint8_t)amin[i];
+  } else {
+    uint8_t* b = codes + (size_t)i * cs + (m >> 1);
+    const uint8_t c = (uint8_t)(amin[i] & 15);
+    *b = (m & 1) ? (uint8_t)(*b | (c << 4)) : c;
+  }
 }
 
 __global__ void k_gather_codes(const uint8_t* __restrict__ src,
@@ -760,18 +778,18 @@ static constexpr float kHalfMax = 65504.0f;  // largest finite f16
 
 __global__ void k_build_S(const float* __restrict__ centroids,
                           const float* __restrict__ codebooks, int32_t nlist,
-                          int32_t M, int32_t dsub, int32_t d,
+                          int32_t M, int32_t ksub, int32_t dsub, int32_t d,
                           __half* __restrict__ S,
                           int32_t* __restrict__ overflow) {
   // one thread per (l, m, code): ||c_sub + cb||^2 over dsub elems
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)nlist * M * 256;
+  int64_t total = (int64_t)nlist * M * ksub;
   if (i >= total) return;
-  int32_t code = (int32_t)(i & 255);
-  int32_t m = (int32_t)((i >> 8) % M);
-  int32_t l = (int32_t)(i / (256 * M));
+  int32_t code = (int32_t)(i % ksub);
+  int32_t m = (int32_t)((i / ksub) % M);
+  int32_t l = (int32_t)(i / ((int64_t)ksub * M));
   const float* c = centroids + (size_t)l * d + m * dsub;
-  const float* cb = codebooks + ((size_t)m * 256 + code) * dsub;
+  const float* cb = codebooks + ((size_t)m * ksub + code) * dsub;
   float acc = 0.f;
   for (int32_t j = 0; j < dsub; j++) {
     float t = c[j] + cb[j];
@@ -917,6 +935,152 @@ __global__ void __launch_bounds__(256, MINB) k_ivfpq_scan(
           if (bitmap) pass = (bitmap[rw >> 5] >> (rw & 31)) & 1;
           cand[cb0 + rw] =
               pass ? pack_cand(acc[r], (uint32_t)rw) : kCandEmpty;
+        }
+      }
+    }
+  }
+}
+
+// THE 4-bit PQ scan (nbits = 4): unit structure, candidate layout and
+// arguments of k_ivfpq_scan; S and T rows have 16 entries, csr_codes rows are
+// M/2 packed bytes (sub-quantizer 2j in the low nibble of byte j), M % 8 == 0.
+// Everything a lookup touches lives in LDS:
+//   U[4 waves][M][16] f32 | S_l[M][16] f16 | codes[256 rows][stride dwords]
+// Per (wave, query) the wave folds U[m][c] = S_l[m][c] - 2*T_q[m][c] (L2) or
+// U = T_q (IP/cosine) and then walks the staged tile: each lane owns 4 rows,
+// reads a row's codes one dword (8 sub-quantizers) at a time and adds
+// U[m][nibble].  Bank argument: all lanes of a wave read
+// the same 16-dword row of U at a time, 16 consecutive banks, equal addresses
+// broadcast; the code row stride is odd, so the 32 lanes of a half wave read
+// their row's dword w from 32 distinct banks.
+__host__ __device__ static inline int32_t pq4_row_stride(int32_t M) {
+  return (M / 8) | 1;  // dwords; odd
+}
+
+__global__ void __launch_bounds__(256) k_ivfpq4_scan(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const uint8_t* __restrict__ csr_codes, const __half* __restrict__ S,
+    const __half* __restrict__ T, const float* __restrict__ coarse_dots,
+    int32_t nlist, int32_t M, const int32_t* __restrict__ inv_offsets,
+    const int32_t* __restrict__ inv_q, const int32_t* __restrict__ inv_rank,
+    const int64_t* __restrict__ qp_off, const int64_t* __restrict__ q_cand_base,
+    int32_t nprobe, int metric, const uint32_t* __restrict__ bitmap,
+    int32_t chunk_rows, uint64_t* __restrict__ cand) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds4[];
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int64_t list_start = csr_offsets[list];
+  const int64_t list_end = csr_offsets[list + 1];
+  const int64_t row_start = list_start + (int64_t)chunk * chunk_rows;
+  const int64_t row_end = min(list_end, row_start + chunk_rows);
+  const int32_t iq0 = inv_offsets[list];
+  const int32_t nql = inv_offsets[list + 1] - iq0;
+  if (nql == 0) return;  // unprobed list (all-chunks launch)
+  constexpr int NW = 4;              // waves per block
+  constexpr int RV = 4;              // rows per lane
+  constexpr int32_t TILE = RV * WAVE;  // == kPqTileRows
+  const int wave_id = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int32_t cw = M / 8;                // dwords of a packed code row
+  const int32_t sw = pq4_row_stride(M);    // its LDS stride
+  const int32_t tab = M * 16;              // entries of one table
+
+  float* U = (float*)lds4 + (size_t)wave_id * tab;
+  __half* Sl = (__half*)(lds4 + (size_t)NW * tab * 4);
+  uint32_t* codes = (uint32_t*)(lds4 + (size_t)NW * tab * 4 + (size_t)tab * 2);
+
+  {  // stage S_l once per unit (32*M bytes)
+    const uint32_t* src_s = (const uint32_t*)(S + (size_t)list * tab);
+    uint32_t* dst_s = (uint32_t*)Sl;
+    for (int32_t w = threadIdx.x; w < tab / 2; w += blockDim.x)
+      dst_s[w] = src_s[w];
+  }
+
+  for (int64_t t0 = row_start; t0 < row_end; t0 += TILE) {
+    const int32_t tn = (int32_t)min((int64_t)TILE, row_end - t0);
+    __syncthreads();  // the previous tile's readers are done
+    {  // stage the packed rows, coalesced in, odd stride out
+      const uint32_t* src =
+          (const uint32_t*)(csr_codes + (size_t)t0 * cw * 4);
+      const int32_t words = tn * cw;
+      for (int32_t w = threadIdx.x; w < words; w += blockDim.x) {
+        const int32_t r = w / cw;
+        codes[r * sw + (w - r * cw)] = src[w];
+      }
+    }
+    // every wave takes every trip (the barriers are block-wide); a wave
+    // past the last probing query idles through them
+    for (int32_t qb = 0; qb < nql; qb += NW) {
+      const int32_t qi = qb + wave_id;
+      const bool active = qi < nql;
+      int32_t q = 0, rank = 0;
+      __syncthreads();  // codes (and S_l) staged; last trip's U consumed
+      if (active) {
+        q = inv_q[iq0 + qi];
+        rank = inv_rank[iq0 + qi];
+        // fold the wave's table, 8 entries per lane and step
+        const uint4* T8 = (const uint4*)(T + (size_t)q * tab);
+        const uint4* S8 = (const uint4*)Sl;
+        for (int32_t i = lane; i < tab / 8; i += WAVE) {
+          const uint4 tv = T8[i];
+          const uint32_t tw[4] = {tv.x, tv.y, tv.z, tv.w};
+          float u[8];
+          if (metric == 0) {
+            const uint4 sv = S8[i];
+            const uint32_t sx[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+              u[2 * j] = __half2float(__ushort_as_half(sx[j] & 0xffff)) -
+                         2.0f * __half2float(__ushort_as_half(tw[j] & 0xffff));
+              u[2 * j + 1] = __half2float(__ushort_as_half(sx[j] >> 16)) -
+                             2.0f * __half2float(__ushort_as_half(tw[j] >> 16));
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+              u[2 * j] = __half2float(__ushort_as_half(tw[j] & 0xffff));
+              u[2 * j + 1] = __half2float(__ushort_as_half(tw[j] >> 16));
+            }
+          }
+          float4* dst = (float4*)(U + (size_t)i * 8);
+          dst[0] = make_float4(u[0], u[1], u[2], u[3]);
+          dst[1] = make_float4(u[4], u[5], u[6], u[7]);
+        }
+      }
+      __syncthreads();  // U complete
+      if (!active) continue;
+      const float dot = coarse_dots[(size_t)q * nlist + list];
+      const int64_t cb0 = q_cand_base[q] +
+                          qp_off[(int64_t)q * nprobe + rank] - list_start;
+      float acc[RV];
+      const uint32_t* crow[RV];
+#pragma unroll
+      for (int r = 0; r < RV; r++) {
+        acc[r] = 0.f;
+        crow[r] = codes + (size_t)(lane + r * WAVE) * sw;
+      }
+      const float* Um = U;
+      for (int32_t w = 0; w < cw; w++) {
+#pragma unroll
+        for (int r = 0; r < RV; r++) {
+          const uint32_t c8 = crow[r][w];
+#pragma unroll
+          for (int j = 0; j < 8; j++)
+            acc[r] += Um[j * 16 + ((c8 >> (4 * j)) & 15)];
+        }
+        Um += 128;
+      }
+#pragma unroll
+      for (int r = 0; r < RV; r++) {
+        const int32_t v = lane + r * WAVE;
+        if (v < tn) {
+          const int64_t rw = t0 + v;
+          // L2: + ||q||^2 at emit; IP and cosine: larger is better
+          const float key = metric == 0 ? acc[r] - 2.0f * dot
+                                        : -(acc[r] + dot);
+          bool pass = true;
+          if (bitmap) pass = (bitmap[rw >> 5] >> (rw & 31)) & 1;
+          cand[cb0 + rw] = pass ? pack_cand(key, (uint32_t)rw) : kCandEmpty;
         }
       }
     }
@@ -2222,6 +2386,12 @@ __global__ void k_gather_rows(const float* __restrict__ src,
   int64_t i = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
   int lane = threadIdx.x % WAVE;
   if (i >= n) return;
+  if (d & 3) {  // PQ subspaces of dsub % 4 != 0: rows are not 16 B aligned
+    const float* s1 = src + (size_t)i * d;
+    float* t1 = dst + (size_t)perm[i] * d;
+    for (int j = lane; j < d; j += WAVE) t1[j] = s1[j];
+    return;
+  }
   const float4* s = (const float4*)(src + (size_t)i * d);
   float4* t = (float4*)(dst + (size_t)perm[i] * d);
   for (int j = lane; j < d / 4; j += WAVE) t[j] = s[j];
@@ -2924,9 +3094,9 @@ void residual(hipStream_t s, const float* x, const int32_t* assign,
 }
 
 void set_code(hipStream_t s, const int32_t* amin, int64_t n, int32_t m,
-              int32_t M, uint8_t* codes) {
+              int32_t code_size, int32_t nbits, uint8_t* codes) {
   if (n) hipLaunchKernelGGL(k_set_code, dim3(ceil_div(n, 256)), dim3(256), 0,
-                            s, amin, n, m, M, codes);
+                            s, amin, n, m, code_size, nbits, codes);
 }
 
 void gather_codes(hipStream_t s, const uint8_t* src, const uint32_t* perm,
@@ -2936,11 +3106,12 @@ void gather_codes(hipStream_t s, const uint8_t* src, const uint32_t* perm,
 }
 
 void build_S(hipStream_t s, const float* centroids, const float* codebooks,
-             int32_t nlist, int32_t M, int32_t dsub, int32_t d, __half* S,
-             int32_t* overflow) {
-  int64_t total = (int64_t)nlist * M * 256;
+             int32_t nlist, int32_t M, int32_t ksub, int32_t dsub, int32_t d,
+             __half* S, int32_t* overflow) {
+  int64_t total = (int64_t)nlist * M * ksub;
   hipLaunchKernelGGL(k_build_S, dim3(ceil_div(total, 256)), dim3(256), 0, s,
-                     centroids, codebooks, nlist, M, dsub, d, S, overflow);
+                     centroids, codebooks, nlist, M, ksub, dsub, d, S,
+                     overflow);
 }
 
 // dynamic LDS one launch may ask for on the current device (160 KiB on
@@ -2960,6 +3131,13 @@ size_t ivfpq_scan_lds(int32_t tile_rows, int32_t M) {
   return (size_t)tile_rows * M + (size_t)M * 256 * 2;
 }
 
+// LDS of one k_ivfpq4_scan block: four per-wave f32 lookup tables, the f16
+// S_l table and the packed code tile with its odd dword row stride
+size_t ivfpq4_scan_lds(int32_t M) {
+  return (size_t)4 * M * 16 * 4 + (size_t)M * 16 * 2 +
+         (size_t)kPqTileRows * pq4_row_stride(M) * 4;
+}
+
 void f32_to_f16(hipStream_t s, const float* in, int64_t n, __half* out) {
   if (n) hipLaunchKernelGGL(k_f32_to_f16, dim3(ceil_div(n, 256)), dim3(256),
                             0, s, in, n, out);
@@ -2973,8 +3151,20 @@ hipError_t ivfpq_scan(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int32_t* inv_rank, const int64_t* qp_off,
                       const int64_t* q_cand_base, int32_t nprobe, int metric,
                       const uint32_t* bitmap, int32_t chunk_rows,
-                      uint64_t* cand) {
+                      uint64_t* cand, int32_t nbits) {
   if (!n_units) return hipSuccess;
+  if (nbits == 4) {
+    const size_t lds4 = ivfpq4_scan_lds(M);
+    if (lds4 > max_launch_lds()) return hipErrorInvalidValue;  // no launch
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_ivfpq4_scan, dim3((uint32_t)n_units), dim3(256),
+                       lds4, s, units, csr_offsets, csr_codes, S, T,
+                       coarse_dots, nlist, M, inv_offsets, inv_q, inv_rank,
+                       qp_off, q_cand_base, nprobe, metric, bitmap,
+                       chunk_rows, cand);
+    return hipGetLastError();
+  }
+  if (nbits != 8) return hipErrorInvalidValue;
   // T-table (L2/L3) traffic per chunk scales as 1/TILE: every staged tile
   // walks each probing query's 48 KB T window once, so the largest tile
   // whose codes + S_l fit LDS wins unless occupancy dominates (A/B'd;

@@ -105,6 +105,7 @@ def _load():
         C.POINTER(_Filter), C.c_void_p, C.c_void_p,
     ]
     lib.dg_mirror_selftest_binary.restype = C.c_int
+    lib.dg_mirror_selftest_pq4.restype = C.c_int
     lib.dg_range_search_binary.argtypes = [
         C.c_void_p, C.c_int64, _u8p, C.c_int32, C.c_int32,
         C.POINTER(_Filter), _i64p, C.POINTER(C.POINTER(C.c_int64)),
@@ -156,6 +157,14 @@ def ivfpq_max_m(device=0):
     return l.dg_ivfpq_max_m(device)
 
 
+def ivfpq_max_m_nbits(device=0, nbits=8):
+    """The same limit for a code width (nbits 4 or 8; 0 for any other)."""
+    l = lib()
+    l.dg_ivfpq_max_m_nbits.argtypes = [C.c_int32, C.c_int32]
+    l.dg_ivfpq_max_m_nbits.restype = C.c_int32
+    return l.dg_ivfpq_max_m_nbits(device, nbits)
+
+
 def make_filter(kind=0, negate=False, min_id=0, max_id=0, ids=None,
                 bitmap=None, bitmap_base=0):
     f = _Filter()
@@ -178,15 +187,17 @@ def make_filter(kind=0, negate=False, min_id=0, max_id=0, ids=None,
 
 class Index:
     def __init__(self, kind, metric, d, nlist=0, m=0, device=-1,
-                 reserve=0, _handle=None):
+                 reserve=0, _handle=None, nbits=8):
+        """nbits: IVF-PQ bits per code, 4 or 8 (0 = the default 8)."""
         self.kind, self.metric, self.d = kind, metric, d
         self.nlist = nlist
         self.m = m
+        self.nbits = nbits if nbits > 0 else 8
         if _handle is not None:
             self.h = _handle
             return
         desc = _Desc(kind=kind, metric=metric, d=d, nlist=nlist,
-                     pq_m=m, pq_nbits=8, device=device, reserve=reserve)
+                     pq_m=m, pq_nbits=nbits, device=device, reserve=reserve)
         h = C.c_void_p()
         _check(lib().dg_index_create(C.byref(h), C.byref(desc)),
                "dg_index_create")
@@ -241,18 +252,22 @@ class Index:
         return out
 
     def set_codebooks(self, codebooks):
-        """codebooks: [m, 256, d//m] float32."""
+        """codebooks: [m, 2**nbits, d//m] float32."""
         cb = np.ascontiguousarray(codebooks, np.float32)
         self.m = cb.shape[0]
         l = lib()
         l.dg_set_codebooks.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
                                        _f32p]
-        _check(l.dg_set_codebooks(self.h, cb.shape[0], 8, cb.reshape(-1)),
+        if cb.ndim != 3 or cb.shape[1] != 1 << self.nbits:
+            raise DgError(f"codebooks must be [m, {1 << self.nbits}, d//m] "
+                          f"at nbits={self.nbits}, got {cb.shape}")
+        _check(l.dg_set_codebooks(self.h, cb.shape[0], self.nbits,
+                                  cb.reshape(-1)),
                "dg_set_codebooks")
 
     def get_codebooks(self):
         dsub = self.d // self.m
-        out = np.empty((self.m, 256, dsub), np.float32)
+        out = np.empty((self.m, 1 << self.nbits, dsub), np.float32)
         l = lib()
         l.dg_get_codebooks.argtypes = [C.c_void_p, _f32p]
         _check(l.dg_get_codebooks(self.h, out.reshape(-1)),
@@ -450,7 +465,15 @@ class Index:
         st = idx.stats()
         idx.kind, idx.metric = st["kind"], st["metric"]
         idx.d, idx.nlist = st["d"], st["nlist"]
-        idx.m = 0
+        idx.m, idx.nbits = 0, 8
+        if idx.kind == IVF_PQ:  # restore the PQ geometry from the handle
+            m, nbits = C.c_int32(), C.c_int32()
+            l = lib()
+            l.dg_pq_params.argtypes = [C.c_void_p, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32)]
+            _check(l.dg_pq_params(h, C.byref(m), C.byref(nbits)),
+                   "dg_pq_params")
+            idx.m, idx.nbits = m.value, nbits.value
         return idx
 
     def last_scan_fused(self):

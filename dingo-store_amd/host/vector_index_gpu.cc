@@ -99,7 +99,8 @@ Status pack_bits(const std::vector<VectorWithId>& v, int32_t dim,
 class GpuIndexBase : public VectorIndex {
  public:
   GpuIndexBase(dg_index_kind kind, MetricType metric, int32_t dim,
-               int32_t nlist, int device, int32_t pq_m = 0) {
+               int32_t nlist, int device, int32_t pq_m = 0,
+               int32_t pq_nbits = 8) {
     metric_ = metric;
     dim_ = dim;
     binary_ = kind == DG_INDEX_BINARY_FLAT || kind == DG_INDEX_BINARY_IVF_FLAT;
@@ -109,7 +110,7 @@ class GpuIndexBase : public VectorIndex {
     desc.d = dim;
     desc.nlist = nlist;
     desc.pq_m = pq_m;
-    desc.pq_nbits = 8;
+    desc.pq_nbits = pq_nbits;
     desc.device = device;
     create_st_ = dg_index_create(&idx_, &desc);
     dg_stats_out s{};
@@ -441,8 +442,8 @@ class GpuBinaryIvfFlatIndex : public GpuIndexBase {
 class GpuIvfPqIndex : public GpuIndexBase {
  public:
   GpuIvfPqIndex(MetricType m, int32_t d, int32_t nlist, int32_t pq_m,
-                int dev)
-      : GpuIndexBase(DG_INDEX_IVF_PQ, m, d, nlist, dev, pq_m) {}
+                int dev, int32_t pq_nbits = 8)
+      : GpuIndexBase(DG_INDEX_IVF_PQ, m, d, nlist, dev, pq_m, pq_nbits) {}
   bool NeedTrain() override { return !IsTrained(); }
   bool NeedToRebuild() override {
     // vector_index_raw_ivf_pq.cc:518-526
@@ -450,6 +451,52 @@ class GpuIvfPqIndex : public GpuIndexBase {
     if (dg_stats(idx_, &s) != DG_OK || !s.is_trained) return false;
     return (s.ntotal / 2) >= train_data_size_;
   }
+};
+
+// An index whose parameters the GPU library refuses (DG_ENOT_SUPPORT at
+// create): every operation answers EVECTOR_NOT_SUPPORT, which is what sends
+// the reader to its brute-force scan (SearchWithBruteForceFallback).
+class GpuUnsupportedIndex : public VectorIndex {
+ public:
+  GpuUnsupportedIndex(MetricType m, int32_t d, std::string why)
+      : metric_(m), dim_(d), why_(std::move(why)) {}
+  int32_t GetDimension() override { return dim_; }
+  MetricType GetMetricType() override { return metric_; }
+  Status GetCount(int64_t& c) override { c = 0; return No(); }
+  Status GetDeletedCount(int64_t& c) override { c = 0; return No(); }
+  Status GetMemorySize(int64_t& b) override { b = 0; return No(); }
+  bool IsExceedsMaxElements(int64_t) override { return false; }
+  Status Add(const std::vector<VectorWithId>&) override { return No(); }
+  Status Upsert(const std::vector<VectorWithId>&) override { return No(); }
+  Status Delete(const std::vector<int64_t>&) override { return No(); }
+  Status Train(const std::vector<VectorWithId>&) override { return No(); }
+  Status Train(std::vector<float>&) override { return No(); }
+  bool IsTrained() override { return false; }
+  bool NeedTrain() override { return false; }
+  bool NeedToRebuild() override { return false; }
+  bool NeedToSave(int64_t) override { return false; }
+  void LockWrite() override {}
+  void UnlockWrite() override {}
+  Status Save(const std::string&) override { return No(); }
+  Status Load(const std::string&) override { return No(); }
+  Status Search(const std::vector<VectorWithId>&, uint32_t,
+                const std::vector<std::shared_ptr<FilterFunctor>>&, bool,
+                const VectorSearchParameter&,
+                std::vector<VectorWithDistanceResult>&) override {
+    return No();
+  }
+  Status RangeSearch(const std::vector<VectorWithId>&, float,
+                     const std::vector<std::shared_ptr<FilterFunctor>>&, bool,
+                     const VectorSearchParameter&,
+                     std::vector<VectorWithDistanceResult>&) override {
+    return No();
+  }
+
+ private:
+  Status No() const { return {kEVectorNotSupport, why_}; }
+  MetricType metric_;
+  int32_t dim_;
+  std::string why_;
 };
 
 }  // namespace
@@ -560,6 +607,22 @@ std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
   auto p = std::make_unique<GpuIvfPqIndex>(metric, dim, ncentroids,
                                            nsubvector, device);
   if (!p->CreateStatus().ok()) return nullptr;
+  return p;
+}
+
+std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
+                                           int32_t ncentroids,
+                                           int32_t nsubvector,
+                                           int32_t nbits_per_idx,
+                                           int device) {
+  // vector_index_ivf_pq.cc:64-66
+  const int32_t nbits = (nbits_per_idx % 64) > 0 ? nbits_per_idx % 64 : 8;
+  auto p = std::make_unique<GpuIvfPqIndex>(metric, dim, ncentroids,
+                                           nsubvector, device, nbits);
+  Status s = p->CreateStatus();
+  if (s.code == kEVectorNotSupport)
+    return std::make_unique<GpuUnsupportedIndex>(metric, dim, s.msg);
+  if (!s.ok()) return nullptr;
   return p;
 }
 
@@ -983,6 +1046,106 @@ extern "C" int dg_mirror_selftest_binary(void) {
           return 126;
       }
     }
+  }
+  return 0;
+}
+
+// ---------------- self-test: IVF-PQ at nbits_per_idx = 4 (GPU) -------------
+extern "C" int dg_mirror_selftest_pq4(void) {
+  using namespace dingogpu;
+  if (dg_device_count() == 0) return 1;
+  const int d = 16, m = 8, nlist = 4, n = 1000;
+  std::vector<VectorWithId> batch(n);
+  uint32_t s = 777;
+  for (int i = 0; i < n; i++) {
+    batch[i].id = i * 5 + 2;
+    batch[i].vector.dimension = d;
+    batch[i].vector.float_values.resize(d);
+    for (int j = 0; j < d; j++) {
+      s = s * 1664525u + 1013904223u;
+      batch[i].vector.float_values[j] = (float)(s >> 8) / 16777216.0f;
+    }
+  }
+  VectorSearchParameter p;
+  p.ivf_flat_nprobe = nlist;
+  p.ivf_pq_nprobe = nlist;
+  // 64 + 4 normalises to 4 like the reference's % 64
+  auto idx = NewIvfPqIndex(MetricType::kL2, d, nlist, m, 64 + 4, -1);
+  if (!idx) return 200;
+  if (idx->IsTrained() || !idx->NeedTrain()) return 201;
+  if (!idx->Train(batch).ok()) return 202;
+  if (!idx->IsTrained()) return 203;
+  if (!idx->Add(batch).ok()) return 204;
+  int64_t cnt = 0;
+  if (!idx->GetCount(cnt).ok() || cnt != n) return 205;
+  std::vector<VectorWithId> queries(batch.begin(), batch.begin() + 40);
+  std::vector<VectorWithDistanceResult> before, after;
+  if (!idx->Search(queries, 4, {}, false, p, before).ok()) return 206;
+  if (before.size() != queries.size()) return 207;
+  for (size_t i = 0; i < queries.size(); i++) {
+    auto& r = before[i].vector_with_distances;
+    if (r.size() != 4) return 208;
+    // a row's own 16-codeword reconstruction is far nearer than any other
+    // row of 1000 uniform points in 16 dimensions
+    if (r[0].vector_with_id.id != queries[i].id) return 209;
+    for (size_t j = 1; j < r.size(); j++)
+      if (r[j].distance < r[j - 1].distance) return 210;
+  }
+  // Save (faiss IwPQ, nbits = 4, packed codes) -> Load -> the same top-4
+  const std::string path = "/tmp/dg_mirror_selftest_pq4." +
+                           std::to_string((long)getpid()) + ".idx";
+  if (!idx->SupportSave() || !idx->Save(path).ok()) return 211;
+  auto fresh = NewIvfPqIndex(MetricType::kL2, d, nlist, m, 4, -1);
+  Status ls = fresh ? fresh->Load(path) : Status{kEInternal, "create"};
+  remove(path.c_str());
+  if (!ls.ok()) return 212;
+  int64_t cnt2 = 0;
+  if (!fresh->GetCount(cnt2).ok() || cnt2 != n || !fresh->IsTrained())
+    return 213;
+  if (!fresh->Search(queries, 4, {}, false, p, after).ok()) return 214;
+  if (after.size() != before.size()) return 215;
+  for (size_t i = 0; i < before.size(); i++) {
+    auto& a = before[i].vector_with_distances;
+    auto& b = after[i].vector_with_distances;
+    if (a.size() != b.size()) return 216;
+    // equal distances; ids equal wherever the distance is not tied (the
+    // row order inside a list may differ after a reload)
+    for (size_t j = 0; j < a.size(); j++) {
+      if (a[j].distance != b[j].distance) return 217;
+      const bool tied =
+          (j && a[j - 1].distance == a[j].distance) ||
+          (j + 1 < a.size() && a[j + 1].distance == a[j].distance) ||
+          j + 1 == a.size();
+      if (!tied && a[j].vector_with_id.id != b[j].vector_with_id.id)
+        return 218;
+    }
+  }
+  // nbits_per_idx = 0 takes the default 8 and creates a working index
+  auto def8 = NewIvfPqIndex(MetricType::kL2, d, nlist, m, 0, -1);
+  if (!def8 || !def8->Train(batch).ok()) return 219;
+  // an unsupported width answers EVECTOR_NOT_SUPPORT and the reader's
+  // brute-force scan serves the search
+  auto odd = NewIvfPqIndex(MetricType::kL2, d, nlist, m, 5, -1);
+  if (!odd) return 220;
+  if (odd->Train(batch).code != kEVectorNotSupport) return 221;
+  std::vector<VectorWithDistanceResult> bf;
+  if (odd->Search(queries, 4, {}, false, p, bf).code != kEVectorNotSupport)
+    return 222;
+  auto factory = [&]() -> RowIterator {
+    auto pos = std::make_shared<size_t>(0);
+    return [&batch, pos](VectorWithId* out) {
+      if (*pos >= batch.size()) return false;
+      *out = batch[(*pos)++];
+      return true;
+    };
+  };
+  if (!SearchWithBruteForceFallback(odd.get(), factory, queries, 4, {}, p, bf)
+           .ok())
+    return 223;
+  if (bf.size() != queries.size()) return 224;
+  for (size_t i = 0; i < queries.size(); i++) {
+    auto& r = bf[i].vector_with_distances;
+    if (r.size() != 4 || r[0].vector_with_id.id != queries[i].id) return 225;
   }
   return 0;
 }

@@ -232,6 +232,15 @@ std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
                                            int32_t ncentroids,
                                            int32_t nsubvector,
                                            int device = -1);
+// The same with nbits_per_idx, normalised like the reference (% 64, 0 -> 8;
+// vector_index_ivf_pq.cc:64-66).  The GPU library runs 4 and 8 (4 packs two
+// codes per byte and needs nsubvector % 8 == 0); for any other value, or a
+// geometry it refuses, the returned index answers EVECTOR_NOT_SUPPORT to
+// every call, so SearchWithBruteForceFallback takes the reader's scan.
+std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
+                                           int32_t ncentroids,
+                                           int32_t nsubvector,
+                                           int32_t nbits_per_idx, int device);
 
 // Binary (Hamming) indexes: dim in bits, vectors carry binary_values of
 // dim / 8 bytes; distances are the integer Hamming distance, passed through
@@ -256,4 +265,8 @@ int dg_mirror_selftest(void);
 // top-1 at distance 0 and the Hamming distance passed through unflipped,
 // range search against a host popcount, Save -> Load -> the same top-4.
 int dg_mirror_selftest_binary(void);
+// IVF-PQ at nbits_per_idx = 4 through the mirror: Train -> Add -> self top-1
+// -> Save -> Load -> the same top-4; an unsupported nbits_per_idx answers
+// EVECTOR_NOT_SUPPORT and the brute-force fallback serves the search.
+int dg_mirror_selftest_pq4(void);
 }

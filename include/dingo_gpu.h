@@ -85,7 +85,9 @@ typedef struct dg_index_desc {
   int32_t nlist;     /* IVF: ncentroids (reference default 2048,
                         src/vector/vector_index.h "kCreateIvfFlatParamNcentroids") */
   int32_t pq_m;      /* IVF-PQ: subquantizers (default 64) */
-  int32_t pq_nbits;  /* IVF-PQ: bits per code (default 8) */
+  int32_t pq_nbits;  /* IVF-PQ: bits per code, 4 or 8 (0 = default 8); every
+                        other value is DG_ENOT_SUPPORT.  nbits = 4 needs
+                        m % 8 == 0 besides d % 4 == 0 and d % m == 0 */
   int32_t device;    /* HIP device ordinal; -1 = current device */
   int64_t reserve;   /* capacity hint in vectors; 0 = grow on demand */
 } dg_index_desc;
@@ -157,12 +159,20 @@ dg_status dg_train(dg_index* idx, int64_t n, const float* x);
  * IVF-PQ index that has codebooks it rebuilds the ADC tables. */
 dg_status dg_set_centroids(dg_index* idx, int32_t nlist, const float* centroids);
 dg_status dg_get_centroids(dg_index* idx, float* out_centroids);
-/* IVF-PQ codebook injection/extraction (m x 256 x (d/m) floats), the PQ
- * analog of dg_set_centroids for oracle-shared parity (requires centroids
- * set first; rebuilds the ADC tables). */
+/* IVF-PQ codebook injection/extraction (m x ksub x (d/m) floats, ksub =
+ * 2^nbits: 256 or 16), the PQ analog of dg_set_centroids for oracle-shared
+ * parity (requires centroids set first; rebuilds the ADC tables).  nbits
+ * must be the index's.
+ * Code layout, on the device, in the own container and in "IwPQ" files:
+ * nbits = 8 stores one byte per sub-quantizer (code_size = m); nbits = 4 is
+ * faiss's generic PQ packing, sub-quantizer 2j in the low nibble of byte j
+ * and 2j+1 in the high nibble (code_size = m/2). */
 dg_status dg_set_codebooks(dg_index* idx, int32_t m, int32_t nbits,
                            const float* codebooks);
 dg_status dg_get_codebooks(dg_index* idx, float* out_codebooks);
+/* The IVF-PQ geometry of an index, as created or loaded (defaults resolved).
+ * DG_EINVAL for any other kind. */
+dg_status dg_pq_params(dg_index* idx, int32_t* m, int32_t* nbits);
 /* IVF-PQ limits.  The scan keeps a 256-row code tile and one list's f16
  * table in LDS, 768 * m bytes per block: dg_index_create, dg_load and
  * dg_load_faiss return DG_ENOT_SUPPORT for m above dg_ivfpq_max_m(device)
@@ -172,6 +182,12 @@ dg_status dg_get_codebooks(dg_index* idx, float* out_codebooks);
  * 65504.  |query_sub . codeword| has the same limit but is not checked
  * (IVF-PQ limits). */
 int32_t dg_ivfpq_max_m(int32_t device);
+/* The same limit per code width.  nbits = 8 is dg_ivfpq_max_m.  The nbits = 4
+ * scan keeps the packed 256-row tile (odd dword row stride), the list's
+ * 16-entry f16 tables and four per-wave f32 lookup tables in LDS, about
+ * 416 * m + 1024 bytes per block: m <= 392 (a multiple of 8) on MI355X.
+ * 0 for any other nbits or if there is no such device. */
+int32_t dg_ivfpq_max_m_nbits(int32_t device, int32_t nbits);
 
 /* ---- mutation (exclusive) ----
  * add restates faiss add_with_ids via VectorIndexIvfFlat::Add
@@ -241,7 +257,7 @@ dg_status dg_load(dg_index** out, const char* path, int32_t device);
  * vector_index_flat.cc:232):
  *   FLAT     -> IndexIDMap2{IndexFlatL2|IndexFlatIP}   ("IxM2"/"IxF2"/"IxFI")
  *   IVF_FLAT -> IndexIVFFlat                            ("IwFl")
- *   IVF_PQ   -> IndexIVFPQ (residual, nbits=8)          ("IwPQ")
+ *   IVF_PQ   -> IndexIVFPQ (residual, nbits 8 or 4)     ("IwPQ")
  * Cosine indexes are written as IP over stored (normalized) vectors, like
  * the reference (vector_index_flat.cc:88-91); on load, pass
  * metric_override = DG_METRIC_COSINE to reconstruct a cosine index from an
