@@ -437,6 +437,8 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
 extern "C" void dg_index_destroy(dg_index* ix) {
   if (!ix) return;
   DeviceGuard g(ix->device);
+  // batched callers drain first; their staging goes with the batcher
+  dg_batcher_destroy(ix->batcher.exchange(nullptr));
   (void)hipStreamSynchronize(ix->stream);
   for (auto b :
        {&ix->d_vectors, &ix->d_ids, &ix->d_assign, &ix->d_centroids,
@@ -2220,7 +2222,8 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
                                     const float* d_x, int32_t k,
                                     int32_t nprobe, const dg_filter* filter,
                                     float* d_out_dist, int64_t* d_out_ids,
-                                    bool binary_entry, const char* fn) {
+                                    bool binary_entry, const char* fn,
+                                    bool may_capture = true) {
   if (!ix || !d_x || !d_out_dist || !d_out_ids || nq <= 0) {
     dg_set_error("bad search args");
     return DG_EINVAL;
@@ -2295,6 +2298,11 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
       ix->times.last_nq = 0;  // per-stage timings not recorded on replays
       return DG_OK;
     }
+    // a batcher flush of 2..4 queries: its size changes from flush to
+    // flush, so it replays a match (above) but never replaces the graph
+    if (!may_capture)
+      return search_core(ix, nq, d_x, k, nprobe, filter, d_out_dist,
+                         d_out_ids);
     // normal run first (sizes every workspace for this shape), then try to
     // capture the same shape over the staging buffers
     dg_status st = search_core(ix, nq, d_x, k, nprobe, filter, d_out_dist,
@@ -2308,6 +2316,7 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
       (void)hipGraphExecDestroy(ix->graph_exec);
       ix->graph_exec = nullptr;
     }
+    std::unique_lock cl(ix->capture_mu);  // no foreign call on the stream
     (void)hipStreamSynchronize(ix->stream);
     const uint64_t gen2 =
         ix->index_gen + g_alloc_gen.load(std::memory_order_relaxed);
@@ -2364,6 +2373,17 @@ extern "C" dg_status dg_search_binary_device(dg_index* ix, int64_t nq,
                             "dg_search_binary_device");
 }
 
+dg_status dg_search_device_flush(dg_index* ix, int64_t nq, const void* d_x,
+                                 int32_t k, int32_t nprobe,
+                                 const dg_filter* filter, float* d_out_dist,
+                                 int64_t* d_out_ids, bool binary_entry) {
+  return search_device_impl(
+      ix, nq, (const float*)d_x, k, nprobe, filter, d_out_dist, d_out_ids,
+      binary_entry,
+      binary_entry ? "dg_search_binary_batched" : "dg_search_batched",
+      /*may_capture=*/nq == 1);
+}
+
 // host-pointer search of either family: x_row_bytes = caller's row stride
 static dg_status search_host_impl(dg_index* ix, int64_t nq, const void* x,
                                   size_t x_row_bytes, int32_t k,
@@ -2382,19 +2402,25 @@ static dg_status search_host_impl(dg_index* ix, int64_t nq, const void* x,
   auto& tls = g_tls_staging.for_device(ix->device);
   dg_dbuf &t_in = tls.in, &t_dist = tls.dist, &t_ids = tls.ids;
   dg_status st;
-  if ((st = dbuf_reserve(t_in, (size_t)nq * x_row_bytes, ix->stream,
-                         false)) != DG_OK ||
-      (st = dbuf_reserve(t_dist, (size_t)nq * k * 4, ix->stream, false)) !=
-          DG_OK ||
-      (st = dbuf_reserve(t_ids, (size_t)nq * k * 8, ix->stream, false)) !=
-          DG_OK)
-    return st;
-  DG_HIP_CHECK(hipMemcpyAsync(t_in.p, x, (size_t)nq * x_row_bytes,
-                              hipMemcpyHostToDevice, ix->stream));
+  {
+    // growth synchronizes the stream, the copy is enqueued on it: neither
+    // may fall into another thread's graph capture (dg_index::capture_mu)
+    std::shared_lock cl(ix->capture_mu);
+    if ((st = dbuf_reserve(t_in, (size_t)nq * x_row_bytes, ix->stream,
+                           false)) != DG_OK ||
+        (st = dbuf_reserve(t_dist, (size_t)nq * k * 4, ix->stream, false)) !=
+            DG_OK ||
+        (st = dbuf_reserve(t_ids, (size_t)nq * k * 8, ix->stream, false)) !=
+            DG_OK)
+      return st;
+    DG_HIP_CHECK(hipMemcpyAsync(t_in.p, x, (size_t)nq * x_row_bytes,
+                                hipMemcpyHostToDevice, ix->stream));
+  }
   st = search_device_impl(ix, nq, (const float*)t_in.p, k, nprobe, filter,
                           (float*)t_dist.p, (int64_t*)t_ids.p, binary_entry,
                           fn);
   if (st != DG_OK) return st;
+  std::shared_lock cl(ix->capture_mu);
   DG_HIP_CHECK(hipMemcpyAsync(out_dist, t_dist.p, (size_t)nq * k * 4,
                               hipMemcpyDeviceToHost, ix->stream));
   DG_HIP_CHECK(hipMemcpyAsync(out_ids, t_ids.p, (size_t)nq * k * 8,

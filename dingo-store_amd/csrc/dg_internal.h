@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
@@ -53,6 +54,19 @@ dg_status dg_ingest_rows(dg_index* ix, int64_t n, const int64_t* ids,
 // assign = null for Flat.
 dg_status dg_ingest_bits(dg_index* ix, int64_t n, const int64_t* ids,
                          const uint8_t* bits, const int32_t* assign);
+
+// One flush of the search batcher (dg_batch.cpp): dg_search_device /
+// dg_search_binary_device under the same locks, except that only a flush of
+// one query may capture the small-batch hipGraph.  A flush of 2..4 queries
+// replays a graph that matches and otherwise runs the kernels, so changing
+// flush sizes never recapture (search batching).
+dg_status dg_search_device_flush(dg_index* ix, int64_t nq, const void* d_x,
+                                 int32_t k, int32_t nprobe,
+                                 const dg_filter* filter, float* d_out_dist,
+                                 int64_t* d_out_ids, bool binary_entry);
+// dg_index_destroy: drains and frees the index's batcher, if it has one
+struct dg_batcher;
+void dg_batcher_destroy(dg_batcher* b);
 
 // Device-side filter descriptor (POD copied into kernel args).
 struct dg_dev_filter {
@@ -209,12 +223,23 @@ struct dg_index {
   dg_dbuf ws_gq, ws_gout;   // fixed staging: queries in, dist+ids out
   bool capturing = false;   // search_core: skip event records in capture
 
+  // dg_batching_enable creates it; it lives until dg_index_destroy
+  std::atomic<dg_batcher*> batcher{nullptr};
+
   std::shared_mutex rw;  // search shared; mutation exclusive
   // Concurrent dg_search calls are SAFE but serialized per index: searches
   // share the workspace buffers and the HIP stream, so execution holds this
   // mutex (the reference serializes device work on one stream anyway;
   // intra-index parallelism comes from batching, SURVEY.md §8b threading).
   std::mutex search_mu;
+  // Stream capture is a property of the stream, not of the capturing thread:
+  // a copy or a synchronize another thread issues on ix->stream while the
+  // small-batch graph is being captured would be recorded into the graph
+  // (with that caller's host pointer) or fail.  The capture holds this
+  // exclusively; the host-pointer entry points and the batcher's flush hold
+  // it shared around the stream calls they make outside search_mu.  Never
+  // held while waiting for search_mu or rw.
+  std::shared_mutex capture_mu;
 };
 
 // ---- kernel launchers (kernels.hip.cpp; authoritative signatures) ----

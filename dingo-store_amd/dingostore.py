@@ -60,6 +60,17 @@ class _Stats(C.Structure):
     ]
 
 
+class _BatchOpts(C.Structure):
+    _fields_ = [("max_batch", C.c_int32), ("max_wait_us", C.c_int32)]
+
+
+class _BatchStats(C.Structure):
+    _fields_ = [
+        ("calls", C.c_int64), ("queries", C.c_int64), ("flushes", C.c_int64),
+        ("max_flush_queries", C.c_int64), ("bypassed", C.c_int64),
+    ]
+
+
 def _load():
     if not os.path.exists(_SO):
         raise DgError(
@@ -115,6 +126,17 @@ def _load():
     lib.dg_load_faiss_binary.argtypes = [C.POINTER(C.c_void_p), C.c_char_p,
                                          C.c_int32]
     lib.dg_free.argtypes = [C.c_void_p]
+    lib.dg_batching_enable.argtypes = [C.c_void_p, C.POINTER(_BatchOpts)]
+    lib.dg_batching_disable.argtypes = [C.c_void_p]
+    lib.dg_batching_stats.argtypes = [C.c_void_p, C.POINTER(_BatchStats)]
+    lib.dg_search_batched.argtypes = lib.dg_search.argtypes
+    lib.dg_search_binary_batched.argtypes = lib.dg_search_binary.argtypes
+    lib.dg_mirror_selftest_batched.restype = C.c_int
+    lib.dg_bench_threads.argtypes = [
+        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f32p, C.c_int64,
+        C.c_int32, C.c_int32,
+    ]
+    lib.dg_bench_threads.restype = C.c_double
     return lib
 
 
@@ -332,6 +354,47 @@ class Index:
             return dist, ids
         _check(lib().dg_search(self.h, nq, q, k, nprobe, fp, dist, ids),
                "dg_search")
+        return dist, ids
+
+    def enable_batching(self, max_batch=0, max_wait_us=0):
+        """Coalesce concurrent search_batched calls of this index into device
+        batches (dg_batching_enable).  max_batch 0 = 64 queries per batch;
+        max_wait_us 0 = a batch never waits for company once the device is
+        free.  Enabling again drains and restarts the statistics."""
+        opts = _BatchOpts(max_batch=max_batch, max_wait_us=max_wait_us)
+        _check(lib().dg_batching_enable(self.h, C.byref(opts)),
+               "dg_batching_enable")
+
+    def disable_batching(self):
+        """Wait for the open batches; later search_batched calls are plain
+        searches."""
+        _check(lib().dg_batching_disable(self.h), "dg_batching_disable")
+
+    def batching_stats(self):
+        s = _BatchStats()
+        _check(lib().dg_batching_stats(self.h, C.byref(s)),
+               "dg_batching_stats")
+        return {f[0]: getattr(s, f[0]) for f in _BatchStats._fields_}
+
+    def search_batched(self, queries, k, nprobe=0, filt=None):
+        """search() for callers on many threads with few queries each: with
+        batching enabled, calls that wait together run as one device batch
+        and each returns its own rows.  ctypes releases the GIL for the
+        call, so Python threads do block and merge here.  Without
+        enable_batching() it is search()."""
+        q = np.ascontiguousarray(
+            queries, np.uint8 if self.is_binary else np.float32)
+        nq = q.shape[0]
+        dist = np.empty((nq, k), np.float32)
+        ids = np.empty((nq, k), np.int64)
+        fp = C.byref(filt) if filt is not None else None
+        if self.is_binary:
+            _check(lib().dg_search_binary_batched(
+                self.h, nq, q, k, nprobe, fp, dist, ids),
+                "dg_search_binary_batched")
+            return dist, ids
+        _check(lib().dg_search_batched(self.h, nq, q, k, nprobe, fp, dist,
+                                       ids), "dg_search_batched")
         return dist, ids
 
     def search_device(self, q_ptr, nq, k, nprobe, dist_ptr, ids_ptr,

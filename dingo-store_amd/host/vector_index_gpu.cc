@@ -12,7 +12,10 @@
 #include <string>
 
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <queue>
+#include <thread>
 #include <unordered_set>
 
 #include <unistd.h>
@@ -261,7 +264,27 @@ class GpuIndexBase : public VectorIndex {
     }
     dg_index_destroy(idx_);
     idx_ = ni;
+    // batching belongs to the dg_index: carry it over to the loaded one
+    if (batching_) return EnableBatching(batch_opts_.max_batch,
+                                         batch_opts_.max_wait_us);
     return Status::OK();
+  }
+
+  // Search then goes through dg_search_batched / dg_search_binary_batched,
+  // which merge the pool's concurrent one-query calls into device batches
+  Status EnableBatching(int32_t max_batch, int32_t max_wait_us) {
+    batch_opts_.max_batch = max_batch;
+    batch_opts_.max_wait_us = max_wait_us;
+    dg_status st = dg_batching_enable(idx_, &batch_opts_);
+    batching_ = st == DG_OK;
+    return from_dg(st);
+  }
+  Status DisableBatching() {
+    batching_ = false;
+    return from_dg(dg_batching_disable(idx_));
+  }
+  Status BatchingStats(dg_batch_stats* out) {
+    return from_dg(dg_batching_stats(idx_, out));
   }
 
   Status Search(const std::vector<VectorWithId>& queries, uint32_t topk,
@@ -294,13 +317,16 @@ class GpuIndexBase : public VectorIndex {
     int32_t nprobe = binary_ ? p.binary_ivf_flat_nprobe : p.ivf_flat_nprobe;
     std::vector<float> dist((size_t)queries.size() * topk);
     std::vector<int64_t> labels((size_t)queries.size() * topk, -1);
+    const auto search_f = batching_ ? dg_search_batched : dg_search;
+    const auto search_b =
+        batching_ ? dg_search_binary_batched : dg_search_binary;
     dg_status st =
-        binary_ ? dg_search_binary(idx_, (int64_t)queries.size(), xb.data(),
-                                   (int32_t)topk, nprobe, dfp, dist.data(),
-                                   labels.data())
-                : dg_search(idx_, (int64_t)queries.size(), x.data(),
-                            (int32_t)topk, nprobe, dfp, dist.data(),
-                            labels.data());
+        binary_ ? search_b(idx_, (int64_t)queries.size(), xb.data(),
+                           (int32_t)topk, nprobe, dfp, dist.data(),
+                           labels.data())
+                : search_f(idx_, (int64_t)queries.size(), x.data(),
+                           (int32_t)topk, nprobe, dfp, dist.data(),
+                           labels.data());
     if (st != DG_OK) return from_dg(st);
     // FillSearchResult shaping (utils.cc:612-655)
     results.clear();
@@ -387,6 +413,8 @@ class GpuIndexBase : public VectorIndex {
   MetricType metric_;
   int32_t dim_;
   bool binary_ = false;
+  bool batching_ = false;  // set before the index is shared with the pool
+  dg_batch_opts batch_opts_{};
   int32_t nlist_created_ = 0;  // nlist_org_ of the reference
   int64_t train_data_size_ = 0;
 };
@@ -638,6 +666,19 @@ std::unique_ptr<VectorIndex> NewBinaryIvfFlatIndex(int32_t dim,
   auto p = std::make_unique<GpuBinaryIvfFlatIndex>(dim, ncentroids, device);
   if (!p->CreateStatus().ok()) return nullptr;
   return p;
+}
+
+Status EnableBatching(VectorIndex* index, int32_t max_batch,
+                      int32_t max_wait_us) {
+  auto* g = dynamic_cast<GpuIndexBase*>(index);
+  if (!g) return {kEVectorNotSupport, "not a GPU index"};
+  return g->EnableBatching(max_batch, max_wait_us);
+}
+
+Status DisableBatching(VectorIndex* index) {
+  auto* g = dynamic_cast<GpuIndexBase*>(index);
+  if (!g) return {kEVectorNotSupport, "not a GPU index"};
+  return g->DisableBatching();
 }
 
 }  // namespace dingogpu
@@ -1148,4 +1189,220 @@ extern "C" int dg_mirror_selftest_pq4(void) {
     if (r.size() != 4 || r[0].vector_with_id.id != queries[i].id) return 225;
   }
   return 0;
+}
+
+// ---------------- self-test: search batching (GPU) ----------------
+namespace {
+
+// the reference pool's call shape: n_threads threads, one query per Search,
+// released together; thread t takes queries t, t + n_threads, ...
+int pool_search(dingogpu::VectorIndex* idx,
+                const std::vector<dingogpu::VectorWithId>& queries,
+                uint32_t topk,
+                const std::vector<std::shared_ptr<dingogpu::FilterFunctor>>& f,
+                const dingogpu::VectorSearchParameter& p, int n_threads,
+                std::vector<dingogpu::VectorWithDistanceResult>* out) {
+  using namespace dingogpu;
+  out->assign(queries.size(), {});
+  std::atomic<int> ready{0}, failed{0};
+  std::vector<std::thread> th;
+  for (int t = 0; t < n_threads; t++)
+    th.emplace_back([&, t] {
+      ready++;
+      while (ready.load() < n_threads) std::this_thread::yield();
+      for (size_t i = t; i < queries.size(); i += n_threads) {
+        std::vector<VectorWithDistanceResult> r;
+        if (!idx->Search({queries[i]}, topk, f, false, p, r).ok() ||
+            r.size() != 1)
+          failed++;
+        else
+          (*out)[i] = std::move(r[0]);
+      }
+    });
+  for (auto& t : th) t.join();
+  return failed.load();
+}
+
+// the comparison rule of batched against direct answers: the same ids,
+// distances within rel (0 = equal)
+bool same_answers(const std::vector<dingogpu::VectorWithDistanceResult>& a,
+                  const std::vector<dingogpu::VectorWithDistanceResult>& b,
+                  float rel) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); i++) {
+    auto& x = a[i].vector_with_distances;
+    auto& y = b[i].vector_with_distances;
+    if (x.size() != y.size()) return false;
+    for (size_t j = 0; j < x.size(); j++) {
+      if (x[j].vector_with_id.id != y[j].vector_with_id.id) return false;
+      if (std::fabs(x[j].distance - y[j].distance) >
+          rel * std::fabs(y[j].distance))
+        return false;
+    }
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int dg_mirror_selftest_batched(void) {
+  using namespace dingogpu;
+  if (dg_device_count() == 0) return 1;
+  const int32_t d = 64, n = 4000, nq = 48, threads = 16;
+  std::vector<VectorWithId> batch(n);
+  uint32_t s = 2024;
+  for (int i = 0; i < n; i++) {
+    batch[i].id = i * 2 + 1;
+    batch[i].vector.dimension = d;
+    batch[i].vector.float_values.resize(d);
+    for (int j = 0; j < d; j++) {
+      s = s * 1664525u + 1013904223u;
+      batch[i].vector.float_values[j] = (s >> 8) * (1.0f / 16777216.0f);
+    }
+  }
+  // queries: rows with a little deterministic noise
+  std::vector<VectorWithId> queries(batch.begin(), batch.begin() + nq);
+  for (auto& q : queries)
+    for (auto& v : q.vector.float_values) {
+      s = s * 1664525u + 1013904223u;
+      v += ((s >> 8) * (1.0f / 16777216.0f) - 0.5f) * 0.1f;
+    }
+  const std::vector<std::shared_ptr<FilterFunctor>> none;
+  const std::vector<std::shared_ptr<FilterFunctor>> lower_half{
+      std::make_shared<RangeFilterFunctor>(0, n)};  // ids 1, 3, .. < n
+  std::vector<VectorWithDistanceResult> direct, direct_f, got;
+
+  // ---- IVF-Flat L2, without and with the region-range filter ----
+  {
+    auto ivf = NewIvfFlatIndex(MetricType::kL2, d, 16);
+    if (!ivf) return 300;
+    VectorSearchParameter p;
+    p.ivf_flat_nprobe = 8;
+    if (!ivf->Train(batch).ok() || !ivf->Add(batch).ok()) return 301;
+    // the same calls unbatched (batching is off until EnableBatching)
+    if (pool_search(ivf.get(), queries, 5, none, p, 1, &direct)) return 302;
+    if (pool_search(ivf.get(), queries, 5, lower_half, p, 1, &direct_f))
+      return 303;
+    for (auto& r : direct_f)
+      for (auto& vd : r.vector_with_distances)
+        if (vd.vector_with_id.id >= n) return 304;
+    // a batch waits up to 1 ms for company here, so that batches form
+    // whatever the scheduling
+    if (!EnableBatching(ivf.get(), 16, 1000).ok()) return 305;
+    if (pool_search(ivf.get(), queries, 5, none, p, threads, &got)) return 306;
+    if (!same_answers(got, direct, 1e-4f)) return 307;
+    if (pool_search(ivf.get(), queries, 5, lower_half, p, threads, &got))
+      return 308;
+    if (!same_answers(got, direct_f, 1e-4f)) return 309;
+    dg_batch_stats bs{};
+    auto* g = dynamic_cast<GpuIndexBase*>(ivf.get());
+    if (!g || !g->BatchingStats(&bs).ok()) return 310;
+    if (bs.calls != 2 * nq || bs.queries != 2 * nq || bs.bypassed != 0)
+      return 311;
+    if (bs.max_flush_queries < 2 || bs.flushes >= 2 * nq) return 312;
+    // off again: Search is the plain path and answers the same
+    if (!DisableBatching(ivf.get()).ok()) return 313;
+    if (pool_search(ivf.get(), queries, 5, none, p, threads, &got)) return 314;
+    if (!same_answers(got, direct, 1e-4f)) return 315;
+    if (!g->BatchingStats(&bs).ok() || bs.calls != 2 * nq) return 316;
+  }
+
+  // ---- Flat inner product: the 1 - score flip survives batching ----
+  {
+    auto flat = NewFlatIndex(MetricType::kInnerProduct, d);
+    if (!flat) return 320;
+    VectorSearchParameter p;
+    if (!flat->Add(batch).ok()) return 321;
+    if (pool_search(flat.get(), queries, 5, none, p, 1, &direct)) return 322;
+    if (!EnableBatching(flat.get()).ok()) return 323;  // defaults: 64, no wait
+    if (pool_search(flat.get(), queries, 5, none, p, threads, &got))
+      return 324;
+    if (!same_answers(got, direct, 1e-4f)) return 325;
+    for (int i = 0; i < nq; i++) {
+      auto& r = got[i].vector_with_distances;
+      if (r.size() != 5) return 326;
+      for (auto& vd : r) {
+        const auto& row = batch[(vd.vector_with_id.id - 1) / 2];
+        double dot = 0;
+        for (int j = 0; j < d; j++)
+          dot += (double)queries[i].vector.float_values[j] *
+                 row.vector.float_values[j];
+        // reported = 1 - score (vector_index_utils.cc:634)
+        if (std::fabs((double)vd.distance - (1.0 - dot)) >
+            1e-4 * std::fabs(dot))
+          return 327;
+      }
+    }
+  }
+
+  // ---- binary Flat: integer distances, equal outputs ----
+  {
+    const int32_t db = 256;
+    std::vector<VectorWithId> rows(n);
+    for (int i = 0; i < n; i++) {
+      rows[i].id = i * 3 + 1;
+      rows[i].vector.dimension = db;
+      rows[i].vector.value_type = ValueType::kUint8;
+      rows[i].vector.binary_values.resize(db / 8);
+      for (auto& v : rows[i].vector.binary_values) {
+        s = s * 1664525u + 1013904223u;
+        v = (uint8_t)(s >> 24);
+      }
+    }
+    std::vector<VectorWithId> bq(rows.begin(), rows.begin() + nq);
+    for (auto& q : bq) q.vector.binary_values[3] ^= 0x5a;
+    auto bin = NewBinaryFlatIndex(db);
+    if (!bin) return 330;
+    VectorSearchParameter p;
+    if (!bin->Add(rows).ok()) return 331;
+    if (pool_search(bin.get(), bq, 5, none, p, 1, &direct)) return 332;
+    if (!EnableBatching(bin.get()).ok()) return 333;
+    if (pool_search(bin.get(), bq, 5, none, p, threads, &got)) return 334;
+    if (!same_answers(got, direct, 0.f)) return 335;
+  }
+
+  // an index that is not GPU-backed has nothing to batch
+  auto odd = NewIvfPqIndex(MetricType::kL2, 16, 4, 8, 5, -1);
+  if (!odd || EnableBatching(odd.get()).code != kEVectorNotSupport) return 340;
+  return 0;
+}
+
+extern "C" double dg_bench_threads(dg_index* idx, int32_t threads,
+                                   int32_t calls_per_thread, int32_t batched,
+                                   const float* q, int64_t nq, int32_t k,
+                                   int32_t nprobe) {
+  if (!idx || !q || threads <= 0 || calls_per_thread <= 0 || nq <= 0 ||
+      k <= 0)
+    return -1.0;
+  dg_stats_out so{};
+  if (dg_stats(idx, &so) != DG_OK) return -1.0;
+  const int32_t d = so.d;
+  std::atomic<int> ready{0}, failed{0};
+  std::chrono::steady_clock::time_point t0;
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; t++)
+    th.emplace_back([&, t] {
+      std::vector<float> dist(k);
+      std::vector<int64_t> ids(k);
+      auto call = [&](int c) {
+        const float* x = q + (size_t)((t * calls_per_thread + c) % nq) * d;
+        const dg_status st =
+            batched ? dg_search_batched(idx, 1, x, k, nprobe, nullptr,
+                                        dist.data(), ids.data())
+                    : dg_search(idx, 1, x, k, nprobe, nullptr, dist.data(),
+                                ids.data());
+        if (st != DG_OK) failed++;
+      };
+      call(0);  // untimed: dg_search allocates this thread's staging
+      ready++;
+      while (ready.load() <= threads) std::this_thread::yield();
+      for (int c = 0; c < calls_per_thread; c++) call(c);
+    });
+  while (ready.load() < threads) std::this_thread::yield();
+  t0 = std::chrono::steady_clock::now();
+  ready++;  // go
+  for (auto& t : th) t.join();
+  const double sec = std::chrono::duration<double>(
+                         std::chrono::steady_clock::now() - t0).count();
+  return failed.load() ? -2.0 : sec;
 }

@@ -254,6 +254,20 @@ std::unique_ptr<VectorIndex> NewBinaryIvfFlatIndex(int32_t dim,
                                                    int32_t ncentroids,
                                                    int device = -1);
 
+// Search batching (off by default).  The reference's search pool calls
+// Search from 16 threads with one query each (vector_index.cc:53-54,244-271)
+// and one index runs one search at a time.  With batching on, Search of a
+// GPU index (float and binary kinds) goes through dg_search_batched /
+// dg_search_binary_batched, which merge the waiting calls into one device
+// batch; every call still returns its own rows (include/dingo_gpu.h, "search
+// batching").  max_batch 0 = 64 queries; max_wait_us 0 = a batch never waits
+// for company once the device is free.  Call it before the index is handed
+// to the pool; the setting survives Load.  EVECTOR_NOT_SUPPORT for an index
+// that is not GPU-backed.  RangeSearch is not batched.
+Status EnableBatching(VectorIndex* index, int32_t max_batch = 0,
+                      int32_t max_wait_us = 0);
+Status DisableBatching(VectorIndex* index);
+
 }  // namespace dingogpu
 
 extern "C" {
@@ -269,4 +283,20 @@ int dg_mirror_selftest_binary(void);
 // -> Save -> Load -> the same top-4; an unsupported nbits_per_idx answers
 // EVECTOR_NOT_SUPPORT and the brute-force fallback serves the search.
 int dg_mirror_selftest_pq4(void);
+// Search batching through the mirror, the reference pool's call shape: 16
+// std::threads, one query per Search, on an L2 IVF-Flat index without and
+// with a RangeFilterFunctor, an inner-product Flat index (the 1 - score
+// flip) and a binary Flat index.  Every answer is compared with the same
+// call made before batching was enabled: the same ids, float distances
+// within 1e-4 relative, binary distances equal.  Batches must have formed.
+int dg_mirror_selftest_batched(void);
+// The second driver of tools/bench_concurrent.py, free of Python threads:
+// `threads` std::threads search the rows of q ([nq x d] float32) round-robin
+// through dg_search (batched = 0) or dg_search_batched, one query per call,
+// `calls_per_thread` times each.  Returns the wall time in seconds, < 0 on
+// an error.
+double dg_bench_threads(dg_index* idx, int32_t threads,
+                        int32_t calls_per_thread, int32_t batched,
+                        const float* q, int64_t nq, int32_t k,
+                        int32_t nprobe);
 }

@@ -21,9 +21,13 @@
  *  - out_ids is padded with -1 where fewer than k results exist, like the
  *    labels pre-fill at src/vector/vector_index_flat.cc:218 and
  *    src/vector/vector_index_ivf_flat.cc:217.
- *  - Thread-safety: concurrent dg_search calls are safe; dg_add / dg_remove /
- *    dg_train / dg_load are exclusive (host RW lock mirroring the
- *    reference's RWLock usage, src/vector/vector_index_ivf_flat.cc:109,225).
+ *  - Thread-safety: concurrent dg_search calls are safe but run one at a
+ *    time per index (they share its stream and workspaces), so N threads
+ *    with one query each get the throughput of one.  dg_search_batched
+ *    merges such calls into device batches (see "search batching" below).
+ *    dg_add / dg_remove / dg_train / dg_load are exclusive (host RW lock
+ *    mirroring the reference's RWLock usage,
+ *    src/vector/vector_index_ivf_flat.cc:109,225).
  */
 #ifndef DINGO_GPU_H_
 #define DINGO_GPU_H_
@@ -228,6 +232,70 @@ dg_status dg_search_device(dg_index* idx, int64_t nq, const float* d_x,
                            int32_t k, int32_t nprobe, const dg_filter* filter,
                            float* d_out_dist, int64_t* d_out_ids);
 dg_status dg_sync(dg_index* idx);
+
+/* ---- search batching: many threads, few queries each ----
+ * The reference's search pool calls Search from 16 threads with one query
+ * per call (src/vector/vector_index.cc:53-54,244-271).  Searches of one
+ * index run one at a time, so that call shape pays the fixed cost of a
+ * search per query.  With batching enabled on an index, dg_search_batched /
+ * dg_search_binary_batched coalesce the calls that are waiting into one
+ * device batch.  There is no dispatcher thread: the first caller of a batch
+ * leads it and flushes as soon as the previous flush has left the device,
+ * so a lone caller pays no added wait, and under load a batch holds
+ * whatever arrived during the previous flush.
+ *  - Not enabled (the default): the _batched calls are dg_search /
+ *    dg_search_binary.
+ *  - Enabled: a call blocks until its own rows are in its own buffers and
+ *    returns what dg_search would for the same arguments.  Arguments are
+ *    checked before the call joins a batch; argument errors, k <= 0 and
+ *    k > 2048 are answered by dg_search itself and never reach a batch.
+ *  - Calls merge if they resolve to the same nprobe (<= 0 => 80, clamped to
+ *    nlist; ignored by Flat) and carry no filter, or RANGE filters with
+ *    equal (min_id, max_id, negate).  A batch runs at the largest k of its
+ *    members and each member receives the first k columns of its rows; that
+ *    is exact, results being best-first under a total order.  A call is
+ *    never split; a batch closes when the next call would overflow it.
+ *  - A call with a SORTED_IDS or BITMAP filter, or with nq >= max_batch,
+ *    runs directly as dg_search and is counted in `bypassed`.
+ *  - Float indexes: which GEMM kernel serves the coarse stage depends on
+ *    the number of rows in the device batch, so a result may differ from
+ *    the nq = 1 call in the last bits of a distance (and in the order of
+ *    rows that tie within them).  Binary results are identical.
+ *  - A flush that fails returns its status to every member, each with the
+ *    message in its own dg_last_error.
+ *  - dg_add / dg_remove / dg_train / the loaders interleave between flushes
+ *    as they do between searches.  dg_batching_disable waits for the open
+ *    batches and makes later _batched calls pass through; dg_index_destroy
+ *    disables first.  Range search is not batched.
+ * max_batch 0 selects 64 (at most 1024); the staging for max_batch queries
+ * (pinned host and device memory) is allocated at enable time and grows
+ * only when a k above 128 arrives.  Enabling again drains, applies the new
+ * options and zeroes the statistics. */
+typedef struct dg_batch_opts {
+  int32_t max_batch;    /* queries per device batch; 0 = default 64 */
+  int32_t max_wait_us;  /* how long an open batch may wait for company after
+                           the device is free; 0 (default) = never wait */
+} dg_batch_opts;
+typedef struct dg_batch_stats {
+  int64_t calls;              /* valid _batched calls since enable */
+  int64_t queries;            /* their query rows */
+  int64_t flushes;            /* device batches run */
+  int64_t max_flush_queries;  /* rows of the largest one */
+  int64_t bypassed;           /* calls run directly (filter kind, nq) */
+} dg_batch_stats;
+dg_status dg_batching_enable(dg_index* idx, const dg_batch_opts* opts);
+dg_status dg_batching_disable(dg_index* idx);
+dg_status dg_batching_stats(dg_index* idx, dg_batch_stats* out);
+dg_status dg_search_batched(dg_index* idx, int64_t nq, const float* x,
+                            int32_t k, int32_t nprobe,
+                            const dg_filter* filter,
+                            float* out_dist /* nq x k */,
+                            int64_t* out_ids /* nq x k */);
+dg_status dg_search_binary_batched(dg_index* idx, int64_t nq,
+                                   const uint8_t* x, int32_t k,
+                                   int32_t nprobe, const dg_filter* filter,
+                                   float* out_dist /* nq x k */,
+                                   int64_t* out_ids /* nq x k */);
 
 /* ---- range search ----
  * Restates VectorIndexIvfFlat::RangeSearch (vector_index_ivf_flat.cc:278-368):
