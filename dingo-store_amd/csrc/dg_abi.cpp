@@ -1449,8 +1449,13 @@ static dg_status finalize_csr(dg_index* ix) {
     }
     dgk::excl_scan_i32_to_i64(ix->stream, d_counts, nlist, d_offsets, sscr);
     dgk::init_cursors(ix->stream, d_offsets, nlist, d_counts);
-    dgk::scatter_perm(ix->stream, (const int32_t*)ix->d_assign.p, n, nullptr,
-                      d_counts, d_perm);
+    // one list: arrival order, so that the internal row (the tie-break of
+    // equal distances) does not depend on the order atomics retire in
+    if (nlist == 1)
+      dgk::identity_perm(ix->stream, n, d_perm);
+    else
+      dgk::scatter_perm(ix->stream, (const int32_t*)ix->d_assign.p, n,
+                        nullptr, d_counts, d_perm);
     if (is_pq) {
       dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_codes.p, d_perm, n,
                         dg_pq_code_size(ix->desc),
@@ -1679,31 +1684,21 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
   DbufGuard g_range(ws_range);
   int64_t* d_rcounts = nullptr;
   uint64_t* d_thr = nullptr;
-  // with_thr = false: only the count/lims/cursor arrays (binary Flat)
-  auto build_thr = [&](bool with_thr = true) -> dg_status {
+  // with_thr: the packed integer threshold of binary IVF (key = the
+  // distance itself).  The float kinds take none: their count / compact
+  // kernels compare the distance range_emit writes with the radius, so a
+  // pre-subtracted threshold cannot round differently from the emitted
+  // number.  Without it only the count/lims/cursor arrays are set up.
+  auto build_thr = [&](bool with_thr) -> dg_status {
     h_thr.resize(with_thr ? nq : 0);
-    if (!with_thr) {
-      // nothing to fill
-    } else if (is_bin) {  // key = the distance itself: no query norm, no sync
-      for (int64_t i = 0; i < nq; i++)
-        h_thr[i] = ((uint64_t)h_enc_f32(rr->radius) << 32);
-    } else if (metric == DG_METRIC_L2) {
-      std::vector<float> h_qn(nq);
-      DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
-      DG_HIP_CHECK(hipMemcpy(h_qn.data(), dqn, (size_t)nq * 4,
-                             hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < nq; i++)
-        h_thr[i] = ((uint64_t)h_enc_f32(rr->radius - h_qn[i]) << 32);
-    } else {
-      for (int64_t i = 0; i < nq; i++)
-        h_thr[i] = ((uint64_t)h_enc_f32(-rr->radius) << 32);
-    }
+    for (int64_t i = 0; i < (int64_t)h_thr.size(); i++)
+      h_thr[i] = ((uint64_t)h_enc_f32(rr->radius) << 32);
     dg_status s2 = dbuf_reserve(ws_range,
                                 (size_t)nq * 8 * 3 + ((size_t)nq + 1) * 8,
                                 ix->stream, false);
     if (s2 != DG_OK) return s2;
-    d_thr = (uint64_t*)ws_range.p;
-    d_rcounts = (int64_t*)(d_thr + nq);
+    d_rcounts = (int64_t*)ws_range.p + nq;
+    d_thr = with_thr ? (uint64_t*)ws_range.p : nullptr;
     if (with_thr)
       DG_HIP_CHECK(hipMemcpyAsync(d_thr, h_thr.data(), (size_t)nq * 8,
                                   hipMemcpyHostToDevice, ix->stream));
@@ -1854,7 +1849,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     if (rr) {
       // range search: count pass + compact pass (GEMM recomputed — range
       // is not the measured hot path)
-      if ((st = build_thr()) != DG_OK) {
+      if ((st = build_thr(false)) != DG_OK) {
         return st;
       }
       for (int64_t ci = 0; ci < nchunks && st == DG_OK; ci++) {
@@ -1866,7 +1861,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
         if (st != DG_OK) break;
         dgk::count_below_dense(ix->stream, (const float*)ix->ws_dots.p,
                                (const float*)ix->d_csr_vnorms.p + c0, nq, cc,
-                               mode, d_bitmap, c0, d_thr, d_rcounts);
+                               mode, d_bitmap, c0, dqn, rr->radius, d_rcounts);
       }
       if (st == DG_OK)
         st = range_finish([&](const int64_t*, int64_t* d_cursors,
@@ -1889,9 +1884,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
             dgk::compact_below_dense(ix->stream,
                                      (const float*)ix->ws_dots.p,
                                      (const float*)ix->d_csr_vnorms.p + c0,
-                                     nq, cc, mode, d_bitmap, c0, d_thr,
-                                     (const int64_t*)d_off2.p, d_cursors,
-                                     d_out);
+                                     nq, cc, mode, d_bitmap, c0, dqn,
+                                     rr->radius, (const int64_t*)d_off2.p,
+                                     d_cursors, d_out);
           }
           (void)hipStreamSynchronize(ix->stream);
           dbuf_free(d_off2);
@@ -2171,9 +2166,10 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
 
     if (rr) {
       // range search over the candidate buffer
-      if ((st = build_thr()) == DG_OK) {
+      if ((st = build_thr(is_bin)) == DG_OK) {
         dgk::count_below(ix->stream, (const uint64_t*)ix->ws_cand.p,
-                         q_cand_base, q_total, d_thr, nq, d_rcounts);
+                         q_cand_base, q_total, d_thr, emit_metric, dqn,
+                         rr->radius, nq, d_rcounts);
         st = range_finish([&](const int64_t*, int64_t* d_cursors,
                               uint64_t* d_out) -> dg_status {
           dg_dbuf d_off2{};
@@ -2183,8 +2179,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
           (void)hipMemcpyAsync(d_off2.p, rr->lims, ((size_t)nq + 1) * 8,
                                hipMemcpyHostToDevice, ix->stream);
           dgk::compact_below(ix->stream, (const uint64_t*)ix->ws_cand.p,
-                             q_cand_base, q_total, d_thr,
-                             (const int64_t*)d_off2.p, nq, d_cursors, d_out);
+                             q_cand_base, q_total, d_thr, emit_metric, dqn,
+                             rr->radius, (const int64_t*)d_off2.p, nq,
+                             d_cursors, d_out);
           (void)hipStreamSynchronize(ix->stream);
           dbuf_free(d_off2);
           return DG_OK;

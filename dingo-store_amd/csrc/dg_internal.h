@@ -363,22 +363,29 @@ void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,
                 const int64_t* ids_lookup, const float* qnorms, int64_t nq,
                 int metric, int add_qnorm, float* out_dist,
                 int64_t* out_ids);
+// Candidate variants: thr != nullptr (binary kinds) admits packed keys below
+// thr[q]; thr == nullptr (float kinds) admits on the number range_emit
+// writes, max(0, key + qnorms[q]) < radius for metric L2 and -key > radius
+// for IP / COSINE (qnorms is read for L2 only).  The dense variants are the
+// float form over a dots chunk, mode 1 (L2) or 2 (IP / COSINE).
 void count_below(hipStream_t s, const uint64_t* cand, const int64_t* base,
-                 const int64_t* total, const uint64_t* thr, int64_t nq,
+                 const int64_t* total, const uint64_t* thr, int metric,
+                 const float* qnorms, float radius, int64_t nq,
                  int64_t* counts);
 void compact_below(hipStream_t s, const uint64_t* cand, const int64_t* base,
-                   const int64_t* total, const uint64_t* thr,
-                   const int64_t* out_off, int64_t nq, int64_t* cursors,
-                   uint64_t* out);
+                   const int64_t* total, const uint64_t* thr, int metric,
+                   const float* qnorms, float radius, const int64_t* out_off,
+                   int64_t nq, int64_t* cursors, uint64_t* out);
 void count_below_dense(hipStream_t s, const float* scores,
                        const float* cnorms, int64_t rows, int64_t cols,
                        int mode, const uint32_t* bitmap, int64_t col_base,
-                       const uint64_t* thr, int64_t* counts);
+                       const float* qnorms, float radius, int64_t* counts);
 void compact_below_dense(hipStream_t s, const float* scores,
                          const float* cnorms, int64_t rows, int64_t cols,
                          int mode, const uint32_t* bitmap, int64_t col_base,
-                         const uint64_t* thr, const int64_t* out_off,
-                         int64_t* cursors, uint64_t* out);
+                         const float* qnorms, float radius,
+                         const int64_t* out_off, int64_t* cursors,
+                         uint64_t* out);
 // IVF-PQ
 void residual(hipStream_t s, const float* x, const int32_t* assign,
               const float* centroids, int64_t n, int32_t d, float* out);
@@ -423,6 +430,7 @@ void dots_mfma(hipStream_t s, const float* X, int64_t M, const float* Y,
                int64_t N, int32_t K, float* C, int64_t ldc);
 void hist_assign(hipStream_t s, const int32_t* assign, int64_t n,
                  int32_t nlist, int32_t* counts);
+void identity_perm(hipStream_t s, int64_t n, uint32_t* perm);
 void scatter_perm(hipStream_t s, const int32_t* assign, int64_t n,
                   const int64_t* offsets_i64, int32_t* cursors32,
                   uint32_t* perm /* dest slot for row i */);

@@ -390,21 +390,59 @@ __global__ void k_fill_units(const int32_t* __restrict__ unit_offsets,
 }
 
 // ---------- range search (radius) ----------
-// candidates (packed u64) below a per-query threshold key.  Strict '<'
-// matches faiss RangeSearch (L2: dist < radius; IP: score > radius).
+// The float kinds admit a row on the very number k_range_emit writes out:
+// range_dist() is that number, and count, compact and emit all call it, so
+// "admitted" and "emitted dist < radius" (IP / COSINE: score > radius)
+// cannot round apart.  Strict comparison, as faiss RangeSearch; a NaN key
+// admits nothing.  The count and compact passes must agree bit for bit (the
+// compact pass writes at offsets sized by the count pass): both go through
+// range_admit() / dense_key() and nothing else.
+__device__ __forceinline__ float range_dist(float key, int metric,
+                                            int add_qnorm, float qn) {
+  if (metric == 0) {  // L2: key may be cnorm-2dot; add qnorm back, clamp
+    float dist = add_qnorm ? key + qn : key;
+    return dist < 0.f ? 0.f : dist;
+  }
+  return -key;  // raw IP score
+}
+__device__ __forceinline__ bool range_admit(float key, int metric, float qn,
+                                            float radius) {
+  const float dist = range_dist(key, metric, 1, qn);
+  return metric == 0 ? dist < radius : dist > radius;
+}
+// mode as k_select_dense
+__device__ __forceinline__ float dense_key(float s, float cn, int mode) {
+  return (mode == 0) ? s : (mode == 1) ? cn - 2.0f * s : -s;
+}
+
+// candidates (packed u64) of a query within the radius.  thr != nullptr
+// (the binary kinds, integer distances): packed key below thr[q], and
+// metric / qnorms / radius are unused.  thr == nullptr (the float kinds):
+// range_admit on the decoded key; qnorms is read for metric 0 only.
+__device__ __forceinline__ bool cand_admit(uint64_t c, bool packed,
+                                           uint64_t t, int metric, float qn,
+                                           float radius) {
+  if (packed) return c < t;
+  return c != kCandEmpty &&
+         range_admit(dec_f32((uint32_t)(c >> 32)), metric, qn, radius);
+}
+
 __global__ void k_count_below(const uint64_t* __restrict__ cand,
                               const int64_t* __restrict__ base,
                               const int64_t* __restrict__ total,
-                              const uint64_t* __restrict__ thr, int64_t nq,
-                              int64_t* __restrict__ counts) {
+                              const uint64_t* __restrict__ thr, int metric,
+                              const float* __restrict__ qnorms, float radius,
+                              int64_t nq, int64_t* __restrict__ counts) {
   __shared__ int64_t lds[256];
   int64_t q = blockIdx.x;
   if (q >= nq) return;
   const uint64_t* seg = cand + base[q];
-  const uint64_t t = thr[q];
+  const bool packed = thr != nullptr;
+  const uint64_t t = packed ? thr[q] : 0;
+  const float qn = (!packed && metric == 0) ? qnorms[q] : 0.f;
   int64_t c = 0;
   for (int64_t i = threadIdx.x; i < total[q]; i += blockDim.x)
-    if (seg[i] < t) c++;
+    if (cand_admit(seg[i], packed, t, metric, qn, radius)) c++;
   lds[threadIdx.x] = c;
   __syncthreads();
   for (int s = blockDim.x / 2; s; s >>= 1) {
@@ -417,43 +455,49 @@ __global__ void k_count_below(const uint64_t* __restrict__ cand,
 __global__ void k_compact_below(const uint64_t* __restrict__ cand,
                                 const int64_t* __restrict__ base,
                                 const int64_t* __restrict__ total,
-                                const uint64_t* __restrict__ thr,
+                                const uint64_t* __restrict__ thr, int metric,
+                                const float* __restrict__ qnorms,
+                                float radius,
                                 const int64_t* __restrict__ out_off,
                                 int64_t nq, int64_t* __restrict__ cursors,
                                 uint64_t* __restrict__ out) {
   int64_t q = blockIdx.x;
   if (q >= nq) return;
   const uint64_t* seg = cand + base[q];
-  const uint64_t t = thr[q];
+  const bool packed = thr != nullptr;
+  const uint64_t t = packed ? thr[q] : 0;
+  const float qn = (!packed && metric == 0) ? qnorms[q] : 0.f;
   for (int64_t i = threadIdx.x; i < total[q]; i += blockDim.x) {
     uint64_t c = seg[i];
-    if (c < t) {
+    if (cand_admit(c, packed, t, metric, qn, radius)) {
       int64_t pos = atomicAdd((unsigned long long*)&cursors[q], 1ull);
       out[out_off[q] + pos] = c;  // host sorts per query afterwards
     }
   }
 }
 
-// dense (Flat) variants over a dots chunk; mode as k_select_dense
+// dense (Flat, float kinds) variants over a dots chunk; mode 1 (L2, key =
+// cnorm - 2 dot, qnorms read) or 2 (IP / COSINE, key = -dot)
 __global__ void k_count_below_dense(const float* __restrict__ scores,
                                     const float* __restrict__ cnorms,
                                     int64_t rows, int64_t cols, int mode,
                                     const uint32_t* __restrict__ bitmap,
                                     int64_t col_base,
-                                    const uint64_t* __restrict__ thr,
+                                    const float* __restrict__ qnorms,
+                                    float radius,
                                     int64_t* __restrict__ counts) {
   __shared__ int64_t lds[256];
   int64_t row = blockIdx.x;
   if (row >= rows) return;
   const float* sr = scores + row * cols;
-  const uint64_t t = thr[row];
+  const int metric = mode == 1 ? 0 : 1;
+  const float qn = mode == 1 ? qnorms[row] : 0.f;
   int64_t c = 0;
   for (int64_t j = threadIdx.x; j < cols; j += blockDim.x) {
     int64_t g = col_base + j;
     if (bitmap && !((bitmap[g >> 5] >> (g & 31)) & 1)) continue;
-    float s = sr[j];
-    float key = (mode == 0) ? s : (mode == 1) ? cnorms[j] - 2.0f * s : -s;
-    if (pack_cand(key, (uint32_t)g) < t) c++;
+    if (range_admit(dense_key(sr[j], cnorms[j], mode), metric, qn, radius))
+      c++;
   }
   lds[threadIdx.x] = c;
   __syncthreads();
@@ -469,23 +513,23 @@ __global__ void k_compact_below_dense(const float* __restrict__ scores,
                                       int64_t rows, int64_t cols, int mode,
                                       const uint32_t* __restrict__ bitmap,
                                       int64_t col_base,
-                                      const uint64_t* __restrict__ thr,
+                                      const float* __restrict__ qnorms,
+                                      float radius,
                                       const int64_t* __restrict__ out_off,
                                       int64_t* __restrict__ cursors,
                                       uint64_t* __restrict__ out) {
   int64_t row = blockIdx.x;
   if (row >= rows) return;
   const float* sr = scores + row * cols;
-  const uint64_t t = thr[row];
+  const int metric = mode == 1 ? 0 : 1;
+  const float qn = mode == 1 ? qnorms[row] : 0.f;
   for (int64_t j = threadIdx.x; j < cols; j += blockDim.x) {
     int64_t g = col_base + j;
     if (bitmap && !((bitmap[g >> 5] >> (g & 31)) & 1)) continue;
-    float s = sr[j];
-    float key = (mode == 0) ? s : (mode == 1) ? cnorms[j] - 2.0f * s : -s;
-    uint64_t c = pack_cand(key, (uint32_t)g);
-    if (c < t) {
+    const float key = dense_key(sr[j], cnorms[j], mode);
+    if (range_admit(key, metric, qn, radius)) {
       int64_t pos = atomicAdd((unsigned long long*)&cursors[row], 1ull);
-      out[out_off[row] + pos] = c;
+      out[out_off[row] + pos] = pack_cand(key, (uint32_t)g);
     }
   }
 }
@@ -499,19 +543,13 @@ __global__ void k_range_emit(const uint64_t* __restrict__ packed,
                              int64_t* __restrict__ out_ids) {
   int64_t q = blockIdx.x;
   if (q >= nq) return;
+  const float qn = (metric == 0 && add_qnorm) ? qnorms[q] : 0.f;
   for (int64_t i = lims[q] + threadIdx.x; i < lims[q + 1];
        i += blockDim.x) {
     uint64_t c = packed[i];
-    float key = dec_f32((uint32_t)(c >> 32));
     uint32_t row = (uint32_t)c;
-    float dist;
-    if (metric == 0) {
-      dist = add_qnorm ? key + qnorms[q] : key;
-      if (dist < 0.f) dist = 0.f;
-    } else {
-      dist = -key;
-    }
-    out_dist[i] = dist;
+    out_dist[i] = range_dist(dec_f32((uint32_t)(c >> 32)), metric, add_qnorm,
+                             qn);
     out_ids[i] = ids_lookup ? ids_lookup[row] : (int64_t)row;
   }
 }
@@ -2379,6 +2417,14 @@ __global__ void k_scatter_perm(const int32_t* __restrict__ assign, int64_t n,
   perm[i] = (uint32_t)atomicAdd(&cursors[assign[i]], 1);
 }
 
+// one list (the Flat kinds): rows keep arrival order.  The atomic cursor of
+// k_scatter_perm would hand them out in whatever order the waves arrive, and
+// equal distances resolve toward the smaller internal row.
+__global__ void k_identity_perm(int64_t n, uint32_t* __restrict__ perm) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) perm[i] = (uint32_t)i;
+}
+
 __global__ void k_gather_rows(const float* __restrict__ src,
                               const uint32_t* __restrict__ perm, int64_t n,
                               int32_t d, float* __restrict__ dst) {
@@ -3054,37 +3100,41 @@ void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,
 }
 
 void count_below(hipStream_t s, const uint64_t* cand, const int64_t* base,
-                 const int64_t* total, const uint64_t* thr, int64_t nq,
+                 const int64_t* total, const uint64_t* thr, int metric,
+                 const float* qnorms, float radius, int64_t nq,
                  int64_t* counts) {
   hipLaunchKernelGGL(k_count_below, dim3((uint32_t)nq), dim3(256), 0, s,
-                     cand, base, total, thr, nq, counts);
+                     cand, base, total, thr, metric, qnorms, radius, nq,
+                     counts);
 }
 
 void compact_below(hipStream_t s, const uint64_t* cand, const int64_t* base,
-                   const int64_t* total, const uint64_t* thr,
-                   const int64_t* out_off, int64_t nq, int64_t* cursors,
-                   uint64_t* out) {
+                   const int64_t* total, const uint64_t* thr, int metric,
+                   const float* qnorms, float radius, const int64_t* out_off,
+                   int64_t nq, int64_t* cursors, uint64_t* out) {
   hipLaunchKernelGGL(k_compact_below, dim3((uint32_t)nq), dim3(256), 0, s,
-                     cand, base, total, thr, out_off, nq, cursors, out);
+                     cand, base, total, thr, metric, qnorms, radius, out_off,
+                     nq, cursors, out);
 }
 
 void count_below_dense(hipStream_t s, const float* scores,
                        const float* cnorms, int64_t rows, int64_t cols,
                        int mode, const uint32_t* bitmap, int64_t col_base,
-                       const uint64_t* thr, int64_t* counts) {
+                       const float* qnorms, float radius, int64_t* counts) {
   hipLaunchKernelGGL(k_count_below_dense, dim3((uint32_t)rows), dim3(256), 0,
                      s, scores, cnorms, rows, cols, mode, bitmap, col_base,
-                     thr, counts);
+                     qnorms, radius, counts);
 }
 
 void compact_below_dense(hipStream_t s, const float* scores,
                          const float* cnorms, int64_t rows, int64_t cols,
                          int mode, const uint32_t* bitmap, int64_t col_base,
-                         const uint64_t* thr, const int64_t* out_off,
-                         int64_t* cursors, uint64_t* out) {
+                         const float* qnorms, float radius,
+                         const int64_t* out_off, int64_t* cursors,
+                         uint64_t* out) {
   hipLaunchKernelGGL(k_compact_below_dense, dim3((uint32_t)rows), dim3(256),
                      0, s, scores, cnorms, rows, cols, mode, bitmap,
-                     col_base, thr, out_off, cursors, out);
+                     col_base, qnorms, radius, out_off, cursors, out);
 }
 
 void residual(hipStream_t s, const float* x, const int32_t* assign,
@@ -3263,6 +3313,11 @@ void scatter_perm(hipStream_t s, const int32_t* assign, int64_t n,
                   uint32_t* perm) {
   hipLaunchKernelGGL(k_scatter_perm, dim3(ceil_div(n, 256)), dim3(256), 0, s,
                      assign, n, cursors, perm);
+}
+
+void identity_perm(hipStream_t s, int64_t n, uint32_t* perm) {
+  hipLaunchKernelGGL(k_identity_perm, dim3(ceil_div(n, 256)), dim3(256), 0, s,
+                     n, perm);
 }
 
 void gather_rows(hipStream_t s, const float* src, const uint32_t* perm,

@@ -300,7 +300,14 @@ dg_status dg_search_binary_batched(dg_index* idx, int64_t nq,
 /* ---- range search ----
  * Restates VectorIndexIvfFlat::RangeSearch (vector_index_ivf_flat.cc:278-368):
  * radius in faiss convention (L2: dist < radius, IP/cos: score > radius; the
- * C++ shim applies the 1-r flip of :302-305); results best-first per query.
+ * C++ shim applies the 1-r flip of :302-305); results best-first per query,
+ * ties toward the smaller id.  A row is admitted on the very float that is
+ * written to out_dists (L2: the squared distance clamped at 0), so every
+ * returned element satisfies dist < radius (IP/cos: score > radius) as a
+ * float32 comparison, and an L2 radius <= 0 returns nothing, the 0.0 of a
+ * query equal to a stored row included (as the reference, which compares
+ * the final value).  Rows whose exact distance is within float32 rounding
+ * of the radius (Flat exact path) may fall on either side.
  * CSR out params: caller frees *out_ids / *out_dists with dg_free. ---- */
 dg_status dg_range_search(dg_index* idx, int64_t nq, const float* x,
                           float radius, const dg_filter* filter,
