@@ -239,9 +239,10 @@ def kth_radius(metric, ref, elig, kth):
 
 def range_radii(metric, ref, elig):
     """[median 5th neighbour, a radius that returns nothing, one that
-    returns every eligible row], float32 values."""
+    returns every eligible row], float32 values.  elig is bool [n] or
+    [nq, n]."""
     sg = better_sign(metric)
-    s = sg * ref[:, elig]
+    s = sg * (ref[:, elig] if elig.ndim == 1 else ref[elig])
     lo, hi = s.min(), s.max()
     nothing = 0.5 * lo if metric == L2 else sg * (lo - 0.25 * (hi - lo))
     everything = sg * (hi + 0.25 * (hi - lo))
