@@ -1342,6 +1342,11 @@ extern "C" dg_status dg_remove(dg_index* ix, int64_t n, const int64_t* ids) {
   return DG_OK;
 }
 
+bool dg_contains_id(dg_index* ix, int64_t id) {
+  std::shared_lock lk(ix->rw);
+  return ix->id_count.count(id) != 0;
+}
+
 static dg_status upsert_impl(dg_index* ix, int64_t n, const int64_t* ids,
                              const void* x, bool binary_entry,
                              const char* fn) {

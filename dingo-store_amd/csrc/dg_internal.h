@@ -68,6 +68,10 @@ dg_status dg_search_device_flush(dg_index* ix, int64_t nq, const void* d_x,
 struct dg_batcher;
 void dg_batcher_destroy(dg_batcher* b);
 
+// The sharded index (dg_shard.cpp) checks presence before it touches a shard:
+// true iff id is a live row of ix.  Takes the read lock itself.
+bool dg_contains_id(dg_index* ix, int64_t id);
+
 // Device-side filter descriptor (POD copied into kernel args).
 struct dg_dev_filter {
   int32_t kind;    // dg_filter_kind
@@ -425,6 +429,13 @@ void emit_results(hipStream_t s, const uint64_t* topk,
                   const int64_t* ids_lookup, const float* qnorms, int64_t nq,
                   int32_t k, int metric, int add_qnorm, float* out_dist,
                   int64_t* out_ids);
+// merge n_lists best-first lists per query into the k_out best under the
+// order of dg_shard_core.h: dists / ids [n_lists][nq][k_in] ->
+// out [nq][k_out], rank placement, one thread per input element.  The caller
+// checks the limits (n_lists <= 32, k_in, k_out <= 2048, block count)
+void merge_lists(hipStream_t s, const float* dists, const int64_t* ids,
+                 int32_t n_lists, int64_t nq, int32_t k_in, int32_t k_out,
+                 int metric, float* out_dist, int64_t* out_ids);
 // k-means / finalize helpers
 void dots_mfma(hipStream_t s, const float* X, int64_t M, const float* Y,
                int64_t N, int32_t K, float* C, int64_t ldc);

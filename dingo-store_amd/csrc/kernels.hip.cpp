@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "dg_internal.h"
+#include "dg_shard_core.h"
 
 #define WAVE 64
 
@@ -283,6 +284,42 @@ __global__ void k_emit(const uint64_t* __restrict__ topk,
   }
   out_dist[i] = dist;
   out_ids[i] = ids_lookup ? ids_lookup[row] : (int64_t)row;
+}
+
+// ---------- merge of best-first lists (sharded index, dg_merge_topk) ----------
+// dists / ids: [n_lists][nq][k_in], every list sorted under the order of
+// dg_shard_core.h.  One thread per input element (q, s, p), p fastest, so a
+// wave's own element loads are consecutive in one list.  The thread finds its
+// element's final rank with one binary search per other list (dg_merge_rank)
+// and, if rank < k_out, writes it to out[q][rank].  The order is total, so
+// the ranks of a query are a permutation: no two threads write one slot and
+// the kernel needs no atomics, LDS or barriers.  Slots at or beyond
+// n_lists * k_in exist only if k_out is larger; the same threads fill them
+// with pads, strided by the element count.
+__global__ void __launch_bounds__(256)
+k_merge_lists(const float* __restrict__ dists, const int64_t* __restrict__ ids,
+              int32_t n_lists, int64_t nq, int32_t k_in, int32_t k_out,
+              int32_t metric, float* __restrict__ out_dist,
+              int64_t* __restrict__ out_ids) {
+  const int64_t per_q = (int64_t)n_lists * k_in;
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nq * per_q) return;
+  const int64_t q = g / per_q;
+  const int32_t j = (int32_t)(g - q * per_q);  // element within the query
+  const int32_t s = j / k_in, p = j - s * k_in;
+  const int64_t rank =
+      dg_merge_rank(dists, ids, n_lists, nq, k_in, metric, q, s, p);
+  if (rank < k_out) {
+    const int64_t self = dg_merge_list_base(nq, k_in, q, s) + p;
+    const int64_t id = ids[self];
+    const int64_t o = q * k_out + rank;
+    out_dist[o] = id < 0 ? 0.0f : dists[self];  // real: bits copied
+    out_ids[o] = id < 0 ? -1 : id;
+  }
+  for (int64_t r = per_q + j; r < k_out; r += per_q) {
+    out_dist[q * k_out + r] = 0.0f;
+    out_ids[q * k_out + r] = -1;
+  }
 }
 
 // ---------- IVF probe machinery ----------
@@ -2883,6 +2920,15 @@ void emit_results(hipStream_t s, const uint64_t* topk,
                   int64_t* out_ids) {
   hipLaunchKernelGGL(k_emit, dim3(ceil_div(nq * k, 256)), dim3(256), 0, s,
                      topk, ids_lookup, qnorms, nq, k, metric, add_qnorm,
+                     out_dist, out_ids);
+}
+
+void merge_lists(hipStream_t s, const float* dists, const int64_t* ids,
+                 int32_t n_lists, int64_t nq, int32_t k_in, int32_t k_out,
+                 int metric, float* out_dist, int64_t* out_ids) {
+  hipLaunchKernelGGL(k_merge_lists,
+                     dim3(ceil_div(nq * n_lists * k_in, 256)), dim3(256), 0,
+                     s, dists, ids, n_lists, nq, k_in, k_out, (int32_t)metric,
                      out_dist, out_ids);
 }
 

@@ -137,6 +137,41 @@ def _load():
         C.c_int32, C.c_int32,
     ]
     lib.dg_bench_threads.restype = C.c_double
+    # list merge and the sharded index
+    lib.dg_merge_topk.argtypes = [
+        C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p, _i64p,
+        _f32p, _i64p, C.c_int32,
+    ]
+    lib.dg_merge_topk_device.argtypes = [
+        C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+    ]
+    _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+    lib.dg_sharded_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(_Desc),
+                                      C.c_int32, _i32p]
+    lib.dg_sharded_destroy.argtypes = [C.c_void_p]
+    lib.dg_sharded_train.argtypes = [C.c_void_p, C.c_int64, _f32p]
+    lib.dg_sharded_set_centroids.argtypes = [C.c_void_p, C.c_int32, _f32p]
+    lib.dg_sharded_get_centroids.argtypes = [C.c_void_p, _f32p]
+    lib.dg_sharded_set_codebooks.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
+                                             _f32p]
+    lib.dg_sharded_get_codebooks.argtypes = [C.c_void_p, _f32p]
+    lib.dg_sharded_add.argtypes = [C.c_void_p, C.c_int64, _i64p, _f32p]
+    lib.dg_sharded_upsert.argtypes = [C.c_void_p, C.c_int64, _i64p, _f32p]
+    lib.dg_sharded_remove.argtypes = [C.c_void_p, C.c_int64, _i64p]
+    lib.dg_sharded_search.argtypes = lib.dg_search.argtypes
+    lib.dg_sharded_search_device.argtypes = lib.dg_search_device.argtypes
+    lib.dg_sharded_sync.argtypes = [C.c_void_p]
+    lib.dg_sharded_range_search.argtypes = [
+        C.c_void_p, C.c_int64, _f32p, C.c_float, C.POINTER(_Filter), _i64p,
+        C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_float)),
+    ]
+    lib.dg_sharded_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
+    lib.dg_sharded_n_shards.argtypes = [C.c_void_p]
+    lib.dg_sharded_n_shards.restype = C.c_int32
+    lib.dg_sharded_shard.argtypes = [C.c_void_p, C.c_int32]
+    lib.dg_sharded_shard.restype = C.c_void_p
+    lib.dg_mirror_selftest_sharded.restype = C.c_int
     return lib
 
 
@@ -227,7 +262,9 @@ class Index:
 
     def close(self):
         if getattr(self, "h", None):
-            lib().dg_index_destroy(self.h)
+            # a shard view (ShardedIndex.shard) borrows its handle
+            if not getattr(self, "_borrowed", False):
+                lib().dg_index_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -571,3 +608,191 @@ def merge_topk(dists, ids, k, metric=L2):
     order = np.lexsort((cat_i, key), axis=1)[:, :k]
     return (np.take_along_axis(cat_d, order, 1),
             np.take_along_axis(cat_i, order, 1))
+
+
+def merge_topk_device(dists, ids, k, metric=L2, device=-1):
+    """merge_topk on the GPU (dg_merge_topk): dists / ids [n_lists, nq,
+    k_in], each list best-first with -1 / 0.0 pads behind the real rows.
+    Returns the k best per query under the library's merge order (is_pad,
+    key, list, position): ties between lists go to the smaller list, not to
+    the smaller id as in the numpy merge_topk.  Real distances keep their
+    bits; pads come out as -1 / 0.0."""
+    d = np.ascontiguousarray(dists, np.float32)
+    i = np.ascontiguousarray(ids, np.int64)
+    if d.ndim != 3 or d.shape != i.shape:
+        raise DgError(f"dists / ids must be [n_lists, nq, k_in], got "
+                      f"{d.shape} and {i.shape}")
+    n_lists, nq, k_in = d.shape
+    od = np.empty((nq, k), np.float32)
+    oi = np.empty((nq, k), np.int64)
+    _check(lib().dg_merge_topk(n_lists, nq, k_in, k, metric, d, i, od, oi,
+                               device), "dg_merge_topk")
+    return od, oi
+
+
+def shard_of(ids, n_shards):
+    """The shard of each id in a ShardedIndex of n_shards shards: the
+    splitmix64 finaliser of the id, modulo n_shards (dg_shard_of)."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(ids, np.int64).astype(np.uint64)
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z % np.uint64(n_shards)).astype(np.int32)
+
+
+class ShardedIndex:
+    """One index over several GPUs of this process (dg_sharded_*): a shard
+    per entry of `devices` (ordinals may repeat), rows routed by id, search
+    fanned out and merged on the first shard's device.  Float kinds only;
+    no save / load, no search batching, no list mask."""
+
+    def __init__(self, kind, metric, d, devices, nlist=0, m=0, nbits=8,
+                 reserve=0):
+        self.kind, self.metric, self.d = kind, metric, d
+        self.nlist, self.m = nlist, m
+        self.nbits = nbits if nbits > 0 else 8
+        devs = np.ascontiguousarray(devices, np.int32).reshape(-1)
+        self.n_shards = len(devs)
+        desc = _Desc(kind=kind, metric=metric, d=d, nlist=nlist, pq_m=m,
+                     pq_nbits=nbits, device=-1, reserve=reserve)
+        h = C.c_void_p()
+        # an empty device list still reaches the library's n_shards check
+        _check(lib().dg_sharded_create(
+            C.byref(h), C.byref(desc), self.n_shards,
+            devs if len(devs) else np.zeros(1, np.int32)),
+            "dg_sharded_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().dg_sharded_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def train(self, x):
+        x = np.ascontiguousarray(x, np.float32)
+        _check(lib().dg_sharded_train(self.h, x.shape[0], x),
+               "dg_sharded_train")
+        if self.kind != FLAT:
+            self.nlist = self.stats()["nlist"]  # n < nlist degrades to 1
+
+    def set_centroids(self, centroids):
+        c = np.ascontiguousarray(centroids, np.float32)
+        _check(lib().dg_sharded_set_centroids(self.h, c.shape[0], c),
+               "dg_sharded_set_centroids")
+        self.nlist = c.shape[0]
+
+    def get_centroids(self):
+        out = np.empty((self.nlist, self.d), np.float32)
+        _check(lib().dg_sharded_get_centroids(self.h, out),
+               "dg_sharded_get_centroids")
+        return out
+
+    def set_codebooks(self, codebooks):
+        """codebooks: [m, 2**nbits, d//m] float32."""
+        cb = np.ascontiguousarray(codebooks, np.float32)
+        if cb.ndim != 3 or cb.shape[1] != 1 << self.nbits:
+            raise DgError(f"codebooks must be [m, {1 << self.nbits}, d//m] "
+                          f"at nbits={self.nbits}, got {cb.shape}")
+        self.m = cb.shape[0]
+        _check(lib().dg_sharded_set_codebooks(self.h, cb.shape[0], self.nbits,
+                                              cb.reshape(-1)),
+               "dg_sharded_set_codebooks")
+
+    def get_codebooks(self):
+        out = np.empty((self.m, 1 << self.nbits, self.d // self.m),
+                       np.float32)
+        _check(lib().dg_sharded_get_codebooks(self.h, out.reshape(-1)),
+               "dg_sharded_get_codebooks")
+        return out
+
+    def add(self, ids, x):
+        ids = np.ascontiguousarray(ids, np.int64)
+        x = np.ascontiguousarray(x, np.float32)
+        _check(lib().dg_sharded_add(self.h, x.shape[0], ids, x),
+               "dg_sharded_add")
+
+    def upsert(self, ids, x):
+        ids = np.ascontiguousarray(ids, np.int64)
+        x = np.ascontiguousarray(x, np.float32)
+        _check(lib().dg_sharded_upsert(self.h, x.shape[0], ids, x),
+               "dg_sharded_upsert")
+
+    def remove(self, ids):
+        ids = np.ascontiguousarray(ids, np.int64)
+        _check(lib().dg_sharded_remove(self.h, len(ids), ids),
+               "dg_sharded_remove")
+
+    def search(self, queries, k, nprobe=0, filt=None):
+        q = np.ascontiguousarray(queries, np.float32)
+        nq = q.shape[0]
+        dist = np.empty((nq, max(k, 0)), np.float32)
+        ids = np.empty((nq, max(k, 0)), np.int64)
+        fp = C.byref(filt) if filt is not None else None
+        _check(lib().dg_sharded_search(self.h, nq, q, k, nprobe, fp, dist,
+                                       ids), "dg_sharded_search")
+        return dist, ids
+
+    def search_device(self, q_ptr, nq, k, nprobe, dist_ptr, ids_ptr,
+                      filt=None):
+        """Device-pointer form: pointers on the first shard's device; the
+        merge is enqueued on the handle's merge stream (sync() waits)."""
+        fp = C.byref(filt) if filt is not None else None
+        _check(lib().dg_sharded_search_device(
+            self.h, nq, C.c_void_p(q_ptr), k, nprobe, fp,
+            C.c_void_p(dist_ptr), C.c_void_p(ids_ptr)),
+            "dg_sharded_search_device")
+
+    def sync(self):
+        _check(lib().dg_sharded_sync(self.h), "dg_sharded_sync")
+
+    def range_search(self, queries, radius, filt=None):
+        """Returns (lims[nq+1], dists, ids), per query best-first with ties
+        toward the smaller id, like Index.range_search."""
+        q = np.ascontiguousarray(queries, np.float32)
+        nq = q.shape[0]
+        lims = np.zeros(nq + 1, np.int64)
+        out_ids = C.POINTER(C.c_int64)()
+        out_dists = C.POINTER(C.c_float)()
+        l = lib()
+        fp = C.byref(filt) if filt is not None else None
+        st = l.dg_sharded_range_search(self.h, nq, q, radius, fp, lims,
+                                       C.byref(out_ids), C.byref(out_dists))
+        try:
+            _check(st, "dg_sharded_range_search")
+            total = int(lims[-1])
+            if total:
+                dists = np.ctypeslib.as_array(out_dists, (total,)).copy()
+                ids = np.ctypeslib.as_array(out_ids, (total,)).copy()
+            else:
+                dists = np.empty(0, np.float32)
+                ids = np.empty(0, np.int64)
+        finally:
+            l.dg_free(C.cast(out_ids, C.c_void_p))
+            l.dg_free(C.cast(out_dists, C.c_void_p))
+        return lims, dists, ids
+
+    def stats(self):
+        s = _Stats()
+        _check(lib().dg_sharded_stats(self.h, C.byref(s)), "dg_sharded_stats")
+        return {f[0]: getattr(s, f[0]) for f in _Stats._fields_
+                if not f[0].startswith("_")}
+
+    def shard(self, i):
+        """Shard i as an Index that borrows the handle: for stats(),
+        get_centroids(), export_assign() and read-only searches.  It stays
+        valid until this ShardedIndex is closed."""
+        h = lib().dg_sharded_shard(self.h, i)
+        if not h:
+            raise DgError(f"shard {i} out of range (n_shards "
+                          f"{self.n_shards})")
+        idx = Index._from_handle(C.c_void_p(h))
+        idx._borrowed = True
+        return idx

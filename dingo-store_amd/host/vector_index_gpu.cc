@@ -527,6 +527,217 @@ class GpuUnsupportedIndex : public VectorIndex {
   std::string why_;
 };
 
+// One index over several devices of this process (dg_sharded_*): the same
+// VectorIndex surface, the same 1 - score flip and error mapping as
+// GpuIndexBase.  Save / Load of a sharded index are not offered.
+class GpuShardedIndex : public VectorIndex {
+ public:
+  GpuShardedIndex(dg_index_kind kind, MetricType metric, int32_t dim,
+                  int32_t nlist, int32_t pq_m, int32_t pq_nbits,
+                  const std::vector<int>& devices)
+      : kind_(kind), metric_(metric), dim_(dim) {
+    dg_index_desc desc{};
+    desc.kind = (int32_t)kind;
+    desc.metric = (int32_t)metric;
+    desc.d = dim;
+    desc.nlist = nlist;
+    desc.pq_m = pq_m;
+    desc.pq_nbits = pq_nbits;
+    std::vector<int32_t> devs(devices.begin(), devices.end());
+    create_st_ = dg_sharded_create(&sh_, &desc, (int32_t)devs.size(),
+                                   devs.data());
+    create_status_ = from_dg(create_st_);
+  }
+  ~GpuShardedIndex() override {
+    if (sh_) dg_sharded_destroy(sh_);
+  }
+  const Status& CreateStatus() const { return create_status_; }
+
+  int32_t GetDimension() override { return dim_; }
+  MetricType GetMetricType() override { return metric_; }
+  Status GetCount(int64_t& count) override {
+    dg_stats_out s{};
+    dg_status st = dg_sharded_stats(sh_, &s);
+    count = s.ntotal;
+    return from_dg(st);
+  }
+  Status GetDeletedCount(int64_t& deleted_count) override {
+    dg_stats_out s{};
+    dg_status st = dg_sharded_stats(sh_, &s);
+    deleted_count = s.deleted_count;
+    return from_dg(st);
+  }
+  Status GetMemorySize(int64_t& bytes) override {
+    dg_stats_out s{};
+    dg_status st = dg_sharded_stats(sh_, &s);
+    bytes = s.device_bytes;
+    return from_dg(st);
+  }
+  bool IsExceedsMaxElements(int64_t) override { return false; }
+  Status Add(const std::vector<VectorWithId>& v) override {
+    if (v.empty()) return {kEillegalParamteters, "vector_with_ids is empty"};
+    std::vector<float> x;
+    std::vector<int64_t> ids;
+    Status s = pack(v, dim_, x, ids);
+    if (!s.ok()) return s;
+    return from_dg(
+        dg_sharded_add(sh_, (int64_t)v.size(), ids.data(), x.data()));
+  }
+  Status Upsert(const std::vector<VectorWithId>& v) override {
+    if (v.empty()) return {kEillegalParamteters, "vector_with_ids is empty"};
+    std::vector<float> x;
+    std::vector<int64_t> ids;
+    Status s = pack(v, dim_, x, ids);
+    if (!s.ok()) return s;
+    return from_dg(
+        dg_sharded_upsert(sh_, (int64_t)v.size(), ids.data(), x.data()));
+  }
+  Status Delete(const std::vector<int64_t>& ids) override {
+    if (ids.empty()) return {kEillegalParamteters, "empty ids"};
+    return from_dg(dg_sharded_remove(sh_, (int64_t)ids.size(), ids.data()));
+  }
+  Status Train(const std::vector<VectorWithId>& v) override {
+    if (v.empty()) return {kEillegalParamteters, "data size invalid"};
+    std::vector<float> x;
+    std::vector<int64_t> ids;
+    Status s = pack(v, dim_, x, ids);
+    if (!s.ok()) return s;
+    return from_dg(dg_sharded_train(sh_, (int64_t)v.size(), x.data()));
+  }
+  Status Train(std::vector<float>& train_datas) override {
+    size_t data_size = train_datas.size() / dim_;
+    if (data_size == 0)
+      return {kEillegalParamteters, "data size invalid"};
+    if (train_datas.size() % dim_ != 0)
+      return {kEillegalParamteters, "dimension not match"};
+    return from_dg(
+        dg_sharded_train(sh_, (int64_t)data_size, train_datas.data()));
+  }
+  bool IsTrained() override {
+    dg_stats_out s{};
+    return dg_sharded_stats(sh_, &s) == DG_OK && s.is_trained;
+  }
+  bool NeedTrain() override {
+    return kind_ != DG_INDEX_FLAT && !IsTrained();
+  }
+  bool NeedToRebuild() override { return false; }
+  bool NeedToSave(int64_t) override { return false; }  // no Save
+  bool SupportSave() override { return false; }
+  // mutation and search of a sharded index lock inside the handle
+  void LockWrite() override {}
+  void UnlockWrite() override {}
+  Status Save(const std::string&) override {
+    return {kEVectorNotSupport, "save of a sharded index is not offered"};
+  }
+  Status Load(const std::string&) override {
+    return {kEVectorNotSupport, "load of a sharded index is not offered"};
+  }
+
+  Status Search(const std::vector<VectorWithId>& queries, uint32_t topk,
+                const std::vector<std::shared_ptr<FilterFunctor>>& filters,
+                bool, const VectorSearchParameter& p,
+                std::vector<VectorWithDistanceResult>& results) override {
+    if (queries.empty())
+      return {kEillegalParamteters, "vector_with_ids is empty"};
+    if (topk == 0) return Status::OK();
+    std::vector<float> x;
+    std::vector<int64_t> ids;
+    Status s = pack(queries, dim_, x, ids);
+    if (!s.ok()) return s;
+    dg_filter df{};
+    dg_filter* dfp = nullptr;
+    if (!filters.empty()) {
+      if (filters.size() == 1 && filters[0]->ToDeviceFilter(&df))
+        dfp = &df;
+      else
+        return {kEVectorNotSupport, "composite filters via reader fallback"};
+    }
+    std::vector<float> dist((size_t)queries.size() * topk);
+    std::vector<int64_t> labels((size_t)queries.size() * topk, -1);
+    dg_status st = dg_sharded_search(
+        sh_, (int64_t)queries.size(), x.data(), (int32_t)topk,
+        kind_ == DG_INDEX_IVF_PQ ? p.ivf_pq_nprobe : p.ivf_flat_nprobe, dfp,
+        dist.data(), labels.data());
+    if (st != DG_OK) return from_dg(st);
+    results.clear();
+    results.resize(queries.size());
+    for (size_t row = 0; row < queries.size(); row++) {
+      for (uint32_t i = 0; i < topk; i++) {
+        size_t pos = row * topk + i;
+        if (labels[pos] < 0) continue;  // padding skipped, utils.cc:622-624
+        VectorWithDistance vd;
+        vd.vector_with_id.id = labels[pos];
+        vd.vector_with_id.vector.dimension = dim_;
+        vd.metric_type = metric_;
+        vd.distance =
+            metric_ == MetricType::kL2 ? dist[pos] : 1.0f - dist[pos];
+        results[row].vector_with_distances.push_back(std::move(vd));
+      }
+    }
+    return Status::OK();
+  }
+
+  Status RangeSearch(const std::vector<VectorWithId>& queries, float radius,
+                     const std::vector<std::shared_ptr<FilterFunctor>>& fs,
+                     bool, const VectorSearchParameter&,
+                     std::vector<VectorWithDistanceResult>& results) override {
+    if (queries.empty())
+      return {kEillegalParamteters, "vector_with_ids is empty"};
+    std::vector<float> x;
+    std::vector<int64_t> ids;
+    Status s = pack(queries, dim_, x, ids);
+    if (!s.ok()) return s;
+    dg_filter df{};
+    dg_filter* dfp = nullptr;
+    if (!fs.empty()) {
+      if (fs.size() == 1 && fs[0]->ToDeviceFilter(&df)) dfp = &df;
+      else return {kEVectorNotSupport, "composite filters via reader"};
+    }
+    float r = metric_ == MetricType::kL2 ? radius : 1.0f - radius;
+    std::vector<int64_t> lims(queries.size() + 1);
+    int64_t* rids = nullptr;
+    float* rdists = nullptr;
+    dg_status st =
+        dg_sharded_range_search(sh_, (int64_t)queries.size(), x.data(), r,
+                                dfp, lims.data(), &rids, &rdists);
+    if (st != DG_OK) return from_dg(st);
+    results.clear();
+    results.resize(queries.size());
+    for (size_t q = 0; q < queries.size(); q++) {
+      for (int64_t i = lims[q]; i < lims[q + 1]; i++) {
+        VectorWithDistance vd;
+        vd.vector_with_id.id = rids[i];
+        vd.vector_with_id.vector.dimension = dim_;
+        vd.metric_type = metric_;
+        vd.distance =
+            metric_ == MetricType::kL2 ? rdists[i] : 1.0f - rdists[i];
+        results[q].vector_with_distances.push_back(std::move(vd));
+      }
+    }
+    dg_free(rids);
+    dg_free(rdists);
+    return Status::OK();
+  }
+
+ private:
+  dg_sharded* sh_ = nullptr;
+  dg_status create_st_ = DG_OK;
+  Status create_status_;
+  dg_index_kind kind_;
+  MetricType metric_;
+  int32_t dim_;
+};
+
+std::unique_ptr<VectorIndex> new_sharded(dg_index_kind kind, MetricType metric,
+                                         int32_t dim, int32_t nlist,
+                                         int32_t pq_m, int32_t pq_nbits,
+                                         const std::vector<int>& devices) {
+  auto p = std::make_unique<GpuShardedIndex>(kind, metric, dim, nlist, pq_m,
+                                             pq_nbits, devices);
+  if (!p->CreateStatus().ok()) return nullptr;
+  return p;
+}
+
 }  // namespace
 
 
@@ -681,7 +892,101 @@ Status DisableBatching(VectorIndex* index) {
   return g->DisableBatching();
 }
 
+std::unique_ptr<VectorIndex> NewShardedFlatIndex(MetricType metric,
+                                                 int32_t dim,
+                                                 std::vector<int> devices) {
+  return new_sharded(DG_INDEX_FLAT, metric, dim, 0, 0, 0, devices);
+}
+
+std::unique_ptr<VectorIndex> NewShardedIvfFlatIndex(MetricType metric,
+                                                    int32_t dim,
+                                                    int32_t ncentroids,
+                                                    std::vector<int> devices) {
+  return new_sharded(DG_INDEX_IVF_FLAT, metric, dim, ncentroids, 0, 0,
+                     devices);
+}
+
+std::unique_ptr<VectorIndex> NewShardedIvfPqIndex(MetricType metric,
+                                                  int32_t dim,
+                                                  int32_t ncentroids,
+                                                  int32_t nsubvector,
+                                                  int32_t nbits_per_idx,
+                                                  std::vector<int> devices) {
+  const int32_t nbits = (nbits_per_idx % 64) > 0 ? nbits_per_idx % 64 : 8;
+  return new_sharded(DG_INDEX_IVF_PQ, metric, dim, ncentroids, nsubvector,
+                     nbits, devices);
+}
+
 }  // namespace dingogpu
+
+// 2-shard Flat indexes on device 0 through VectorIndex::Search.  The rows
+// are the unit vectors e_0 .. e_5 scaled by (id + 1), so every distance is
+// exact in float32 and the expected lists are known: checks the order, the
+// 1 - score flip (IP) and that pads are skipped (k above the row count),
+// then Delete / Upsert routing and the not-supported Save / Load.
+extern "C" int dg_mirror_selftest_sharded(void) {
+  using namespace dingogpu;
+  if (dg_device_count() == 0) return 1;
+  const int32_t d = 8, n = 6;
+  std::vector<VectorWithId> rows(n);
+  for (int i = 0; i < n; i++) {
+    rows[i].id = 100 + i;
+    rows[i].vector.dimension = d;
+    rows[i].vector.float_values.assign(d, 0.f);
+    rows[i].vector.float_values[i] = (float)(i + 1);
+  }
+  VectorWithId q;  // e_2 * 3: the row of id 102 itself
+  q.vector.dimension = d;
+  q.vector.float_values.assign(d, 0.f);
+  q.vector.float_values[2] = 3.f;
+  VectorSearchParameter p;
+  std::vector<VectorWithDistanceResult> res;
+  for (MetricType m : {MetricType::kL2, MetricType::kInnerProduct}) {
+    auto idx = NewShardedFlatIndex(m, d, {0, 0});
+    if (!idx) return 10;
+    if (!idx->Add(rows).ok()) return 11;
+    int64_t cnt = 0;
+    if (!idx->GetCount(cnt).ok() || cnt != n) return 12;
+    // k = 10 > 6 rows: four pads per query, all skipped
+    if (!idx->Search({q}, 10, {}, false, p, res).ok()) return 13;
+    if (res.size() != 1 || (int)res[0].vector_with_distances.size() != n)
+      return 14;
+    const auto& top = res[0].vector_with_distances;
+    if (top[0].vector_with_id.id != 102) return 15;
+    if (m == MetricType::kL2) {
+      // |3 e_2 - (i+1) e_i|^2 = 9 + (i+1)^2 for i != 2, 0 for i = 2
+      if (top[0].distance != 0.f) return 16;
+      if (top[1].vector_with_id.id != 100 || top[1].distance != 10.f)
+        return 17;
+      if (top[5].vector_with_id.id != 105 || top[5].distance != 45.f)
+        return 18;
+    } else {
+      // scores: 9 for id 102 and 0 for the rest; dingo reports 1 - score
+      if (top[0].distance != 1.f - 9.f) return 19;
+      for (int i = 1; i < n; i++)
+        if (top[i].distance != 1.f) return 20;
+    }
+    for (int i = 1; i < n; i++)
+      if (top[i - 1].distance > top[i].distance) return 21;
+    if (!idx->Delete({102}).ok()) return 22;
+    if (idx->Delete({102}).code != kEVectorInvalid) return 23;
+    if (idx->Add({rows[0]}).code != kEVectorIdDuplicated) return 24;
+    if (!idx->Search({q}, 1, {}, false, p, res).ok()) return 25;
+    if (res[0].vector_with_distances.size() != 1 ||
+        res[0].vector_with_distances[0].vector_with_id.id == 102)
+      return 26;
+    VectorWithId moved = rows[5];  // id 105 moves onto the query
+    moved.vector.float_values = q.vector.float_values;
+    if (!idx->Upsert({moved}).ok()) return 27;
+    if (!idx->Search({q}, 1, {}, false, p, res).ok()) return 28;
+    if (res[0].vector_with_distances[0].vector_with_id.id != 105) return 29;
+    if (idx->Save("/nonexistent").code != kEVectorNotSupport ||
+        idx->Load("/nonexistent").code != kEVectorNotSupport)
+      return 30;
+  }
+  if (NewShardedFlatIndex(MetricType::kL2, d, {}) != nullptr) return 31;
+  return 0;
+}
 
 // ---------------- self-test (GPU) ----------------
 extern "C" int dg_mirror_selftest(void) {

@@ -268,6 +268,29 @@ Status EnableBatching(VectorIndex* index, int32_t max_batch = 0,
                       int32_t max_wait_us = 0);
 Status DisableBatching(VectorIndex* index);
 
+// One index sharded over several GPUs of this process (dg_sharded_*,
+// include/dingo_gpu.h): devices holds one HIP ordinal per shard (1 to 32
+// entries; an ordinal may repeat, which puts several shards on one device).
+// Rows are routed to shards by id, Search fans out to all of them and merges
+// on the first shard's device; the surface, the 1 - score flip and the error
+// mapping are those of the single-device indexes.  Save and Load answer
+// EVECTOR_NOT_SUPPORT (SupportSave() is false), LockWrite / UnlockWrite are
+// no-ops (the handle locks inside) and search batching is not offered.
+// nullptr if the library refuses the parameters.
+std::unique_ptr<VectorIndex> NewShardedFlatIndex(MetricType metric,
+                                                 int32_t dim,
+                                                 std::vector<int> devices);
+std::unique_ptr<VectorIndex> NewShardedIvfFlatIndex(MetricType metric,
+                                                    int32_t dim,
+                                                    int32_t ncentroids,
+                                                    std::vector<int> devices);
+std::unique_ptr<VectorIndex> NewShardedIvfPqIndex(MetricType metric,
+                                                  int32_t dim,
+                                                  int32_t ncentroids,
+                                                  int32_t nsubvector,
+                                                  int32_t nbits_per_idx,
+                                                  std::vector<int> devices);
+
 }  // namespace dingogpu
 
 extern "C" {
@@ -290,6 +313,11 @@ int dg_mirror_selftest_pq4(void);
 // call made before batching was enabled: the same ids, float distances
 // within 1e-4 relative, binary distances equal.  Batches must have formed.
 int dg_mirror_selftest_batched(void);
+// 2-shard Flat indexes (both shards on device 0) through the mirror, L2 and
+// inner product, on rows whose distances are exact in float32: the merged
+// order, the 1 - score flip, pads skipped at k above the row count, Delete /
+// Add / Upsert contracts across shards, Save / Load not supported.
+int dg_mirror_selftest_sharded(void);
 // The second driver of tools/bench_concurrent.py, free of Python threads:
 // `threads` std::threads search the rows of q ([nq x d] float32) round-robin
 // through dg_search (batched = 0) or dg_search_batched, one query per call,

@@ -422,6 +422,121 @@ dg_status dg_load_faiss_binary(dg_index** out, const char* path,
  * list-sharded deployments: mask[l] != 0 => list l is scanned here. */
 dg_status dg_set_list_mask(dg_index* idx, const uint8_t* mask /* nlist */);
 
+/* ---- merging best-first lists on the device ----
+ * dists / ids are [n_lists][nq][k_in] result lists as dg_search returns
+ * them (best first, padded with -1 / 0.0 behind the real rows); out is
+ * [nq][k_out], the k_out best of each query's n_lists * k_in elements.
+ * The order is strict and total: an element is smaller iff
+ * (is_pad, key, list, pos) is lexicographically smaller, is_pad = id < 0,
+ * key = the orderable image of the distance (L2) or of the negated score
+ * (IP, COSINE; metric is a dg_metric), list / pos = where it stood in the
+ * input.  -0.0 orders directly before +0.0 (for IP, score +0.0 before -0.0);
+ * a real +inf distance still precedes every pad.  Every input list must be
+ * sorted under that order, which the results of dg_search are.  Real
+ * distances are copied bit for bit; pads, and the slots at or beyond
+ * n_lists * k_in when k_out is larger, come out as -1 / 0.0f.
+ * Limits: 1 <= n_lists <= 32, 1 <= k_in <= 2048, 1 <= k_out <= 2048
+ * (DG_EINVAL otherwise).  This is the merge for results of sibling indexes,
+ * for instance the regions of a split.
+ * dg_merge_topk takes host pointers, runs on `device` (-1 = the current
+ * one) and returns when out is written.  dg_merge_topk_device takes
+ * pointers on the current device and enqueues on `stream` (a hipStream_t,
+ * NULL = the default stream) without synchronising. */
+dg_status dg_merge_topk(int32_t n_lists, int64_t nq, int32_t k_in,
+                        int32_t k_out, int32_t metric, const float* dists,
+                        const int64_t* ids, float* out_dist,
+                        int64_t* out_ids, int32_t device);
+dg_status dg_merge_topk_device(int32_t n_lists, int64_t nq, int32_t k_in,
+                               int32_t k_out, int32_t metric,
+                               const float* d_dists, const int64_t* d_ids,
+                               float* d_out_dist, int64_t* d_out_ids,
+                               void* stream);
+
+/* ---- sharded index: one index over several GPUs of one process ----
+ * A dg_sharded is n_shards ordinary indexes of one descriptor, one per
+ * entry of devices[]; entries may repeat (several shards on one device is
+ * legal: it is how the whole path runs on a single GPU).  Rows are routed by
+ * id: shard = splitmix64(id) % n_shards, stateless, so an id always lives on
+ * the same shard and ids are unique across shards.  Centroids and IVF-PQ
+ * codebooks are replicated bit-identically, so every shard probes the same
+ * lists.  A search fans out to every shard at the caller's k, gathers the
+ * shards' lists into one slab on shard 0's device (the merge device) and
+ * merges them there with the kernel behind dg_merge_topk.
+ *
+ *  - create: 1 <= n_shards <= 32 and valid device ordinals, else DG_EINVAL;
+ *    devices = NULL puts every shard on device 0.  desc.device is ignored,
+ *    desc.reserve is divided among the shards.  Float kinds only: a binary
+ *    kind answers DG_ENOT_SUPPORT.  Every limit of dg_index_create holds per
+ *    shard and is reported with that call's own error text; on any failure
+ *    no shard is left alive.
+ *  - train runs once, on shard 0 (already trained => OK no-op); its
+ *    centroids, and for IVF-PQ its codebooks, are read back and installed on
+ *    the other shards.  set_centroids / set_codebooks install on every
+ *    shard, get_* read shard 0.
+ *  - add / upsert / remove partition the rows on the host and hand every
+ *    shard its part.  The all-or-nothing contracts hold for the whole call:
+ *    a negative id (DG_EINVAL), an id twice in one call or (add) already
+ *    present (DG_EID_DUPLICATED), an untrained index (DG_ENOT_TRAINED) and
+ *    a remove with a missing id (DG_ENOT_FOUND) are answered before any
+ *    shard is touched.  A device failure inside one shard is returned with
+ *    that shard's message and is not rolled back on the others.
+ *  - search has the semantics of dg_search: k <= 0 is an OK no-op, k > 2048
+ *    DG_ENOT_SUPPORT, nprobe defaults and clamps per shard as in dg_search,
+ *    an untrained IVF index returns all -1, padding is -1 / 0.0, a filter of
+ *    any kind goes unchanged to every shard, cosine is normalised by the
+ *    shards.  Ties between shards resolve toward the smaller shard.  The
+ *    host form copies in and out and synchronises.  The _device form takes
+ *    pointers on the merge device and enqueues the merge on the handle's
+ *    merge stream; dg_sharded_sync waits for it.  Every shard's search is
+ *    issued from its own worker thread (owned by the handle), so shards on
+ *    different devices overlap.  A shard that fails returns its status and
+ *    message; the other shards are drained, the merge is not run.
+ *    Searches of one handle run one at a time.
+ *  - range_search: every shard's dg_range_search, each query's rows
+ *    concatenated on the host and sorted best-first, ties toward the smaller
+ *    id (the order of dg_range_search); CSR results freed with dg_free.
+ *  - stats: counts and bytes summed over the shards, stage times the maximum
+ *    over the shards, the merge kernel's time added to last_select_ms.
+ *  - dg_sharded_shard returns the borrowed dg_index of shard i (NULL if out
+ *    of range) for inspection: dg_stats, dg_get_centroids, dg_export_assign.
+ *    Mutating it directly breaks the routing.
+ * Not offered: save / load of a sharded index (save the shards through
+ * dg_sharded_shard, or rebuild), search batching, binary kinds, and the list
+ * mask (the shards are row-sharded). */
+typedef struct dg_sharded dg_sharded; /* opaque */
+dg_status dg_sharded_create(dg_sharded** out, const dg_index_desc* desc,
+                            int32_t n_shards, const int32_t* devices);
+void dg_sharded_destroy(dg_sharded* sh);
+dg_status dg_sharded_train(dg_sharded* sh, int64_t n, const float* x);
+dg_status dg_sharded_set_centroids(dg_sharded* sh, int32_t nlist,
+                                   const float* centroids);
+dg_status dg_sharded_get_centroids(dg_sharded* sh, float* out_centroids);
+dg_status dg_sharded_set_codebooks(dg_sharded* sh, int32_t m, int32_t nbits,
+                                   const float* codebooks);
+dg_status dg_sharded_get_codebooks(dg_sharded* sh, float* out_codebooks);
+dg_status dg_sharded_add(dg_sharded* sh, int64_t n, const int64_t* ids,
+                         const float* x);
+dg_status dg_sharded_upsert(dg_sharded* sh, int64_t n, const int64_t* ids,
+                            const float* x);
+dg_status dg_sharded_remove(dg_sharded* sh, int64_t n, const int64_t* ids);
+dg_status dg_sharded_search(dg_sharded* sh, int64_t nq, const float* x,
+                            int32_t k, int32_t nprobe,
+                            const dg_filter* filter,
+                            float* out_dist /* nq x k */,
+                            int64_t* out_ids /* nq x k */);
+dg_status dg_sharded_search_device(dg_sharded* sh, int64_t nq,
+                                   const float* d_x, int32_t k,
+                                   int32_t nprobe, const dg_filter* filter,
+                                   float* d_out_dist, int64_t* d_out_ids);
+dg_status dg_sharded_sync(dg_sharded* sh);
+dg_status dg_sharded_range_search(dg_sharded* sh, int64_t nq, const float* x,
+                                  float radius, const dg_filter* filter,
+                                  int64_t* lims /* nq+1 */,
+                                  int64_t** out_ids, float** out_dists);
+dg_status dg_sharded_stats(dg_sharded* sh, dg_stats_out* out);
+int32_t dg_sharded_n_shards(dg_sharded* sh);
+dg_index* dg_sharded_shard(dg_sharded* sh, int32_t i);
+
 /* ---- wrapper-lifecycle lock (LockWrite/UnlockWrite,
  * vector_index.h:192-193): the exclusive lock the reference wrapper takes
  * around its fork-save window; must be released by the same thread. ---- */
