@@ -86,6 +86,13 @@ static bool scan_fused_enabled() {
   return !(e && e[0] == '0' && e[1] == '\0');
 }
 
+// DG_SCAN_MFMA=0 runs the fused top-k scan on the VALU kernel
+// (k_ivf_scan_pipe) instead of k_ivf_scan_mfma; read per call likewise.
+static bool scan_mfma_enabled() {
+  const char* e = getenv("DG_SCAN_MFMA");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
 // Blocks per launch of the binary Flat range kernel; more columns than that
 // covers are scanned in several launches.  DG_RANGE_SPAN_BLOCKS lowers it
 // so that tests reach the multi-launch path at small sizes (read per call).
@@ -2057,6 +2064,8 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                        k <= dg_index::kScanFuseMaxK &&
                        nq * partial_per_q <= ub_cand && scan_fused_enabled();
     ix->last_scan_fused = fused;
+    const bool mfma = fused && scan_mfma_enabled();
+    ix->last_scan_mfma = mfma;
     if (fused) {
       if ((st = dbuf_reserve(ix->ws_partial,
                              (size_t)std::max<int64_t>(nq * partial_per_q, 1) *
@@ -2157,7 +2166,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                            (const float*)ix->d_csr_vnorms.p, dq, d,
                            inv_offsets32, inv_q, inv_rank, np, metric,
                            d_bitmap, chunk_rows, k, ix->cpl_max,
-                           (uint64_t*)ix->ws_partial.p);
+                           (uint64_t*)ix->ws_partial.p, mfma);
       else
         dgk::ivf_scan_col(ix->stream, units, total_units,
                           (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
@@ -2286,9 +2295,11 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
     const size_t dist_bytes = (size_t)nq * k * 4;
     const size_t ids_bytes = (size_t)nq * k * 8;
     const bool fused_now = scan_fused_enabled();  // captured into the graph
+    const bool mfma_now = scan_mfma_enabled();    // likewise
     if (ix->graph_exec && ix->graph_nq == (int32_t)nq &&
         ix->graph_k == k && ix->graph_np == nprobe &&
-        ix->graph_fused == fused_now && ix->graph_gen == gen) {
+        ix->graph_fused == fused_now && ix->graph_mfma == mfma_now &&
+        ix->graph_gen == gen) {
       DG_HIP_CHECK(hipMemcpyAsync(ix->ws_gq.p, d_x, q_bytes,
                                   hipMemcpyDeviceToDevice, ix->stream));
       DG_HIP_CHECK(hipGraphLaunch(ix->graph_exec, ix->stream));
@@ -2341,6 +2352,7 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
           ix->graph_k = k;
           ix->graph_np = nprobe;
           ix->graph_fused = fused_now;
+          ix->graph_mfma = mfma_now;
           // capture itself allocates nothing (warm run sized buffers),
           // so gen2 still describes the captured pointers
           ix->graph_gen = gen2;
@@ -2807,6 +2819,12 @@ extern "C" int dg_last_scan_fused(dg_index* ix) {
   if (!ix) return 0;
   std::lock_guard sg(ix->search_mu);
   return ix->last_scan_fused ? 1 : 0;
+}
+
+extern "C" int dg_last_scan_mfma(dg_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard sg(ix->search_mu);
+  return ix->last_scan_mfma ? 1 : 0;
 }
 
 extern "C" dg_status dg_stats(dg_index* ix, dg_stats_out* out) {

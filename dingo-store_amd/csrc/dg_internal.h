@@ -209,6 +209,7 @@ struct dg_index {
   // per-wave top-k slots of the fused IVF-Flat scan (replaces ws_cand there)
   dg_dbuf ws_partial;
   bool last_scan_fused = false;  // path of the last search_core IVF scan
+  bool last_scan_mfma = false;   // ... and whether it was k_ivf_scan_mfma
 
   // timing
   hipEvent_t ev[12] = {};
@@ -222,6 +223,7 @@ struct dg_index {
   hipGraphExec_t graph_exec = nullptr;
   int32_t graph_nq = 0, graph_k = 0, graph_np = 0;
   bool graph_fused = false;  // DG_SCAN_FUSED state the graph was captured in
+  bool graph_mfma = false;   // DG_SCAN_MFMA state, likewise
   uint64_t graph_gen = 0;   // generation the graph was captured at
   uint64_t index_gen = 1;   // bumped on finalize/mutation/buffer growth
   dg_dbuf ws_gq, ws_gout;   // fixed staging: queries in, dist+ids out
@@ -349,7 +351,9 @@ void ivf_scan_col(hipStream_t s, const uint32_t* units, int32_t n_units,
 // IVF-Flat top-k scan with the per-wave selection fused in: writes the k
 // (<= dg_index::kScanFuseMaxK) smallest candidates of each wave to
 // partial[nq][nprobe][cpl_max][chunk_rows/256][k]; the caller presets
-// partial to 0xff bytes (empty) and merges it with select_u64.
+// partial to 0xff bytes (empty) and merges it with select_u64.  mfma picks
+// k_ivf_scan_mfma (f32 MFMA dots) over k_ivf_scan_pipe (VALU dots); both
+// fill the slots with the same bits.
 void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                    const int64_t* csr_offsets, const int32_t* chunk_off,
                    const int64_t* chunk_base, const float* tvec,
@@ -357,7 +361,7 @@ void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                    const int32_t* inv_offsets, const int32_t* inv_q,
                    const int32_t* inv_rank, int32_t nprobe, int metric,
                    const uint32_t* bitmap, int32_t chunk_rows, int32_t k,
-                   int32_t cpl_max, uint64_t* partial);
+                   int32_t cpl_max, uint64_t* partial, bool mfma);
 void transpose_chunks(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int64_t* csr_offsets, const int32_t* chunk_off,
                       const int64_t* chunk_base, const float* rowmajor,

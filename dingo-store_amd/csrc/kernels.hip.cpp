@@ -1623,6 +1623,314 @@ __global__ void __launch_bounds__(256, 1) k_ivf_scan_pipe(
   }
 }
 
+// ---------- f32-MFMA fused top-k scan (IVF-Flat top-k default) ----------
+// Same inputs, grid, query-tile loop and partial-slot output as
+// k_ivf_scan_pipe<QTM,true,true>; the (row, query) dots come from
+// v_mfma_f32_16x16x4_f32, whose result is a k-ordered fmaf chain with one
+// rounding per product — the same bits as the VALU kernels' ascending-dim
+// chain from 0.  For lane l, g = l>>4, i = l&15:
+//   A (queries): lane (g,i) holds q_i[k0+g]
+//   B (rows)   : one float4 per lane at col[(k0+g)*nrows_pad + rb+64m+4i],
+//                m = 0..3; component x feeds tile (m,x), whose column i is
+//                row rb+64m+4i+x
+//   D          : lane (g,j), reg r = dot(query 4g+r, row rb+64m+4j+x)
+// A k-step (4 dims) is 4 loads and 16 MFMAs into 16 independent
+// accumulators.  The loads are plain C++ in a modulo-unrolled 4-stage loop
+// (one named buffer set per stage), so the compiler tracks what is in
+// flight and places its own counted waits; the sched_barrier keeps each
+// stage's re-issue right behind that stage's MFMAs.
+// Queries are staged permuted, [d/16][QTM][g 4][s 4] for dim 16kb+4s+g, so
+// one ds_read_b128 gives a lane its A operands for four k-steps.
+typedef float dg_acc4 __attribute__((ext_vector_type(4)));
+
+// Lane id from mbcnt, seeded through an empty asm so that each use site
+// computes it (and everything derived from it) afresh: with wave_id in an
+// SGPR the kernel then holds no work-item id, and nothing computed from
+// one, in registers across the dim loop (at 168 VGPRs that spills).
+__device__ __forceinline__ int dg_lane_id_fresh() {
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u,
+                                        __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
+
+// min over each 16-lane row (uniform within the row afterwards)
+__device__ __forceinline__ uint32_t dg_row16_min_u32(uint32_t v) {
+#define DG_DPP(ctrl)                                                      \
+  ((uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, (ctrl), 0xf, 0xf,    \
+                                         false))
+  v = min(v, DG_DPP(0xB1));   // quad_perm [1,0,3,2]
+  v = min(v, DG_DPP(0x4E));   // quad_perm [2,3,0,1]
+  v = min(v, DG_DPP(0x141));  // row_half_mirror
+  v = min(v, DG_DPP(0x140));  // row_mirror
+#undef DG_DPP
+  return v;
+}
+
+// Per-wave top-k for the MFMA register layout.  For a fixed reg r the four
+// 16-lane rows hold four different queries (4g+r), each row's 16 lanes x 16
+// tiles being that query's 256 rows, so one row-wise DPP ladder serves four
+// queries per round.  Extract-min on the 32-bit key, then, among the live
+// entries holding that key, on the chunk-local row (64m+4j+x is not
+// monotone in lane order, so the tie needs its own min).  `live` rather
+// than the key value marks what is still a candidate, so a real key that
+// encodes as 0xffffffff still ranks by the u64 order.  The winner's lane
+// stores slot `rnd`; the tail keeps the host's kCandEmpty preset.
+// Must be entered by ALL 64 lanes.
+__device__ __forceinline__ void dg_scan_topk_epilogue_mfma(
+    const dg_acc4 (&acc)[4][4], const int64_t* cbase, int64_t wslot,
+    const float* __restrict__ vnorms, int32_t nrows, int32_t rb, int64_t row0,
+    int32_t qt, int metric, const uint32_t* __restrict__ bitmap, int32_t kf,
+    uint64_t* __restrict__ partial) {
+  const int lane = dg_lane_id_fresh();
+  const int g = lane >> 4, j = lane & 15;
+  // rows past the chunk read the chunk's last row (rb < nrows_pad, so
+  // nrows >= 1) and are masked out: no per-entry branch
+  bool okb[16];
+  float vn[16];
+  const float* vnb = vnorms + row0;
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const int32_t rl = rb + 64 * (e >> 2) + 4 * j + (e & 3);
+    const int32_t rc = min(rl, nrows - 1);
+    bool ok = rl < nrows;
+    if (bitmap) {
+      const int64_t r = row0 + rc;
+      ok = ok && ((bitmap[r >> 5] >> (r & 31)) & 1);
+    }
+    vn[e] = (metric == 0) ? vnb[rc] : 0.f;
+    okb[e] = ok;
+  }
+  uint32_t okm = 0;  // shifted in from the top: no per-bit constants
+#pragma unroll
+  for (int e = 15; e >= 0; e--) okm = (okm << 1) | (okb[e] ? 1u : 0u);
+  const uint32_t rlo = (uint32_t)(row0 + rb);
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    if (r >= qt) break;  // wave-uniform: no row of lanes has query 4g+r
+    const int jq = 4 * g + r;
+    const bool act = jq < qt;
+    uint32_t live = act ? okm : 0u;
+    const int64_t cb = act ? cbase[jq] + wslot : 0;
+    uint32_t kx[16];
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+      const float a = acc[e >> 2][e & 3][r];
+      const float key = (metric == 0) ? vn[e] - 2.0f * a : -a;
+      kx[e] = ((live >> e) & 1u) ? enc_f32(key) : 0xffffffffu;
+    }
+    for (int32_t rnd = 0; rnd < kf; rnd++) {
+      uint32_t m = kx[0];
+#pragma unroll
+      for (int e = 1; e < 16; e++) m = min(m, kx[e]);
+      const uint32_t wm = dg_row16_min_u32(m);
+      uint32_t eq = 0;
+#pragma unroll
+      for (int e = 15; e >= 0; e--) eq = (eq << 1) | (kx[e] == wm ? 1u : 0u);
+      eq &= live;
+      // entries ascend in row within a lane, so the lowest set bit is the
+      // lane's smallest row holding the key
+      const uint32_t ce = eq ? (uint32_t)__builtin_ctz(eq) : 16u;
+      const uint32_t ridx =
+          eq ? (ce >> 2) * 64u + 4u * (uint32_t)j + (ce & 3u) : 0xffffffffu;
+      const uint32_t wr = dg_row16_min_u32(ridx);
+      if (__ballot(wr != 0xffffffffu) == 0) break;  // every query exhausted
+      const bool win = ridx == wr && eq != 0;
+      const uint32_t sel = win ? ce : 16u;
+#pragma unroll
+      for (int e = 0; e < 16; e++)
+        kx[e] = (sel == (uint32_t)e) ? 0xffffffffu : kx[e];
+      if (win) {
+        live &= ~(1u << ce);
+        partial[cb + rnd] = ((uint64_t)wm << 32) | (uint64_t)(rlo + wr);
+      }
+    }
+  }
+}
+
+template <int QTM>
+__global__ void __launch_bounds__(256, 3) k_ivf_scan_mfma(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const float* __restrict__ tvec, const float* __restrict__ vnorms,
+    const float* __restrict__ queries, int32_t d,
+    const int32_t* __restrict__ inv_offsets, const int32_t* __restrict__ inv_q,
+    const int32_t* __restrict__ inv_rank, int32_t nprobe, int metric,
+    const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
+    uint64_t* __restrict__ partial, int32_t kf, int32_t cpl_max) {
+  static_assert(QTM <= 16 && QTM % 4 == 0, "one 16-query MFMA tile");
+  // [nper][QTM][4][4] floats, then cbase[QTM]
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __builtin_assume(d % 4 == 0 && d > 0);
+  const int32_t nks = d >> 2;          // k-steps of 4 dims
+  const int32_t nper = (nks + 3) >> 2;  // periods of 4 k-steps
+  int64_t* cbase = (int64_t*)(smem + (size_t)nper * QTM * 16);
+
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t nrows_pad = (nrows + 3) & ~3;
+  const float* col = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+  const int64_t row0 = list_start + (int64_t)chunk * chunk_rows;
+  const int32_t iq0 = inv_offsets[list];
+  const int32_t nql = inv_offsets[list + 1] - iq0;
+
+  // wave_id in an SGPR keeps rb and all it feeds scalar
+  const int wave_id =
+      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  // bytes per k-step (4 columns); a chunk is at most 8192 x 1024 floats,
+  // so 32 bits hold every byte offset into it
+  const uint32_t kstepb = (uint32_t)nrows_pad * 16u;
+
+  for (int32_t t0 = 0; t0 < nql; t0 += QTM) {
+    const int32_t qt = min(QTM, nql - t0);
+    __syncthreads();
+    // float4 t of query j holds dims 4t..4t+3 = 16kb + 4s + g for g = 0..3
+    // (kb = t>>2, s = t&3); absent queries and absent dims are zero
+    const int tid = wave_id * WAVE + dg_lane_id_fresh();
+#pragma unroll 1
+    for (int32_t j = 0; j < QTM; j++) {
+      const float4* src =
+          j < qt ? (const float4*)(queries +
+                                   (size_t)inv_q[iq0 + t0 + j] * d)
+                 : nullptr;
+      for (int32_t t = tid; t < nper * 4; t += blockDim.x) {
+        float4 v = float4{0.f, 0.f, 0.f, 0.f};
+        if (src && t < nks) v = src[t];
+        float* dst = smem + ((size_t)(t >> 2) * QTM + j) * 16 + (t & 3);
+        dst[0] = v.x;
+        dst[4] = v.y;
+        dst[8] = v.z;
+        dst[12] = v.w;
+      }
+    }
+    if (tid < QTM) {
+      const int32_t j = tid;
+      int64_t cb = 0;
+      if (j < qt)
+        cb = ((((int64_t)inv_q[iq0 + t0 + j] * nprobe +
+                inv_rank[iq0 + t0 + j]) * cpl_max + chunk) *
+              (chunk_rows / (WAVE * 4))) * kf;
+      cbase[j] = cb;
+    }
+    __syncthreads();
+
+    // rb is wave-uniform: a wave runs a 256-row block whole (all 64 lanes
+    // reach the epilogue converged) or skips it, leaving its slots at the
+    // preset kCandEmpty
+    for (int32_t rb = wave_id * WAVE * 4; rb < nrows_pad; rb += 4 * WAVE * 4) {
+      const int64_t wslot = (int64_t)(rb / (WAVE * 4)) * kf;
+      const int lane = dg_lane_id_fresh();
+      const int g = lane >> 4, i = lane & 15;
+      // lanes past the chunk's rows re-read its first rows (no new cache
+      // lines, nothing outside the chunk); the epilogue discards their sums
+      // byte offsets from a wave-uniform column pointer: a chunk is at
+      // most 8192 x 1024 floats, so 32 bits hold them
+      uint32_t voff[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const int32_t rr = rb + 64 * m + 4 * i;
+        voff[m] = ((uint32_t)g * (uint32_t)nrows_pad +
+                   (uint32_t)(rr < nrows_pad ? rr : 0)) * 4u;
+      }
+      const dg_acc4* ap = (const dg_acc4*)smem + (i < QTM ? i : 0) * 4 + g;
+
+      // (zero through an empty asm: as a known constant the compiler keeps
+      // a zero vector live across the dim loop and spills it)
+      float z = 0.f;
+      asm volatile("" : "+v"(z));
+      dg_acc4 acc[4][4];
+#pragma unroll
+      for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int x = 0; x < 4; x++) acc[m][x] = dg_acc4{z, z, z, z};
+      dg_acc4 b0[4], b1[4], b2[4], b3[4];
+      auto issue = [&](dg_acc4 (&b)[4], int32_t ks) {
+        // readfirstlane hides the k-step offset from loop strength
+        // reduction (which would keep 16 per-lane 64-bit pointers and
+        // spill) and pins it to an SGPR: scalar base + 32-bit lane offset
+        const uint32_t uo =
+            __builtin_amdgcn_readfirstlane((uint32_t)ks * kstepb);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+          b[m] = *(const dg_acc4*)((const char*)col + (voff[m] + uo));
+      };
+      auto compute = [&](const dg_acc4 (&b)[4], float a) {
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+#pragma unroll
+          for (int x = 0; x < 4; x++)
+            acc[m][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                a, b[m][x], acc[m][x], 0, 0, 0);
+      };
+      auto qload = [&]() {
+        dg_acc4 a = *ap;
+        ap += QTM * 4;
+        if (QTM < 16 && i >= QTM) a = dg_acc4{0.f, 0.f, 0.f, 0.f};
+        return a;
+      };
+
+      // modulo schedule, period = 4 stages = 16 dims; a stage is re-issued
+      // for the next period as soon as its MFMAs are out
+      // (the prologue issues all four stages in the loop's order so the
+      // compiler's wait counts agree at the loop head; for d < 16 the
+      // absent stages re-read the last column and are never consumed)
+      issue(b0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b1, min(1, nks - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b2, min(2, nks - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b3, min(3, nks - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      int32_t ks = 0;
+      for (; ks + 8 <= nks; ks += 4) {  // the next period is whole too
+        const dg_acc4 a = qload();
+        compute(b0, a.x);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b0, ks + 4);
+        compute(b1, a.y);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b1, ks + 5);
+        compute(b2, a.z);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b2, ks + 6);
+        compute(b3, a.w);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b3, ks + 7);
+      }
+      if (ks + 4 < nks) {  // whole period followed by a 1..3-step one
+        const int32_t rem = nks - ks - 4;
+        const dg_acc4 a = qload();
+        compute(b0, a.x);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b0, ks + 4);
+        compute(b1, a.y);
+        __builtin_amdgcn_sched_barrier(0);
+        if (rem > 1) issue(b1, ks + 5);
+        compute(b2, a.z);
+        __builtin_amdgcn_sched_barrier(0);
+        if (rem > 2) issue(b2, ks + 6);
+        compute(b3, a.w);
+        ks += 4;
+      }
+      {  // last period: 1..4 k-steps; absent steps are skipped, not padded
+        const int32_t rem = nks - ks;
+        const dg_acc4 a = qload();
+        compute(b0, a.x);
+        if (rem > 1) compute(b1, a.y);
+        if (rem > 2) compute(b2, a.z);
+        if (rem > 3) compute(b3, a.w);
+      }
+      dg_scan_topk_epilogue_mfma(acc, cbase, wslot, vnorms, nrows, rb, row0,
+                                 qt, metric, bitmap, kf, partial);
+    }
+  }
+}
+
 // ---------- generalized drain pipeline (v5, DG_SCAN_VARIANT=16..18) ----
 // SAFE-mode generalization of k_ivf_scan_pipe: S stages x 4 dims issued as
 // one batch at block end, ONE vmcnt(0) drain at the next block's head
@@ -3114,8 +3422,28 @@ void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                    const int32_t* inv_offsets, const int32_t* inv_q,
                    const int32_t* inv_rank, int32_t nprobe, int metric,
                    const uint32_t* bitmap, int32_t chunk_rows, int32_t k,
-                   int32_t cpl_max, uint64_t* partial) {
+                   int32_t cpl_max, uint64_t* partial, bool mfma) {
   if (!n_units) return;
+  if (mfma) {
+    // same tile ladder; the LDS image is padded to whole 16-dim periods
+#define DG_MFMA_LAUNCH(QTM)                                                 \
+  do {                                                                      \
+    size_t lds = (size_t)((d + 15) / 16) * (QTM) * 64 + (QTM) * 8;          \
+    hipLaunchKernelGGL((k_ivf_scan_mfma<(QTM)>), dim3((uint32_t)n_units),   \
+                       dim3(256), lds, s, units, csr_offsets, chunk_off,    \
+                       chunk_base, tvec, vnorms, queries, d, inv_offsets,   \
+                       inv_q, inv_rank, nprobe, metric, bitmap, chunk_rows, \
+                       partial, k, cpl_max);                                \
+  } while (0)
+    if (d <= 2304)
+      DG_MFMA_LAUNCH(16);
+    else if (d <= 4608)
+      DG_MFMA_LAUNCH(8);
+    else
+      DG_MFMA_LAUNCH(4);
+#undef DG_MFMA_LAUNCH
+    return;
+  }
   // same tile ladder as the default ivf_scan_col pipeline
 #define DG_PIPE_LAUNCH(QTM)                                                 \
   do {                                                                      \

@@ -584,6 +584,14 @@ class Index:
         l.dg_last_scan_fused.restype = C.c_int
         return bool(l.dg_last_scan_fused(self.h))
 
+    def last_scan_mfma(self):
+        """True if that fused scan ran the f32-MFMA kernel, False for the
+        VALU kernel (DG_SCAN_MFMA=0) or an unfused search."""
+        l = lib()
+        l.dg_last_scan_mfma.argtypes = [C.c_void_p]
+        l.dg_last_scan_mfma.restype = C.c_int
+        return bool(l.dg_last_scan_mfma(self.h))
+
     def stats(self):
         s = _Stats()
         _check(lib().dg_stats(self.h, C.byref(s)), "dg_stats")

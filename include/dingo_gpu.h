@@ -550,6 +550,9 @@ void dg_last_error(char* buf, int64_t len);
  * the per-wave top-k inside the scan, 0 if it stored every candidate
  * (range search, IVF-PQ, large k, oversized slots, DG_SCAN_FUSED=0). */
 int dg_last_scan_fused(dg_index* idx);
+/* 1 if that fused scan ran the f32-MFMA kernel (the default), 0 if it ran
+ * the VALU kernel (DG_SCAN_MFMA=0) or the search was not fused at all. */
+int dg_last_scan_mfma(dg_index* idx);
 int dg_device_count(void);
 /* Library self-identification: returns a static string with build arch. */
 const char* dg_build_info(void);
