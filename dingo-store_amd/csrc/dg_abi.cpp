@@ -93,6 +93,19 @@ static bool scan_mfma_enabled() {
   return !(e && e[0] == '0' && e[1] == '\0');
 }
 
+// DG_SCAN_PAIR=0 keeps every query tile on k_ivf_scan_mfma (no pair
+// kernel); 1, 2 or 4 set the pair kernel's grid.y (A/B switch for the
+// measurement in DESIGN.md §Pair scan); anything else is the default.
+// Read per call likewise.  Returns 0 for off, else grid.y.
+static int32_t scan_pair_py() {
+  const char* e = getenv("DG_SCAN_PAIR");
+  if (e && e[0] && e[1] == '\0') {
+    if (e[0] == '0') return 0;
+    if (e[0] == '1' || e[0] == '2' || e[0] == '4') return e[0] - '0';
+  }
+  return dg_index::kScanPairPY;
+}
+
 // Blocks per launch of the binary Flat range kernel; more columns than that
 // covers are scanned in several launches.  DG_RANGE_SPAN_BLOCKS lowers it
 // so that tests reach the multi-launch path at small sizes (read per call).
@@ -455,7 +468,7 @@ extern "C" void dg_index_destroy(dg_index* ix) {
         &ix->d_cb_norms, &ix->ws_T, &ix->ws_Tf32, &ix->ws_queries, &ix->ws_qnorms,
         &ix->ws_dots, &ix->ws_probes, &ix->ws_inv, &ix->ws_cand, &ix->ws_units,
         &ix->ws_small, &ix->ws_topk, &ix->ws_scan, &ix->ws_seg, &ix->ws_gq,
-        &ix->ws_gout, &ix->ws_bm, &ix->ws_partial})
+        &ix->ws_gout, &ix->ws_bm, &ix->ws_partial, &ix->ws_qimage})
     dbuf_free(*b);
   if (ix->graph_exec) (void)hipGraphExecDestroy(ix->graph_exec);
   for (auto& e : ix->ev)
@@ -2066,6 +2079,16 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     ix->last_scan_fused = fused;
     const bool mfma = fused && scan_mfma_enabled();
     ix->last_scan_mfma = mfma;
+    // lists probed by 17+ queries: two query tiles per pass over the rows
+    const int32_t pair_py =
+        mfma && dg_scan_pair_applies((int32_t)d, nq) ? scan_pair_py() : 0;
+    ix->last_scan_pair = pair_py > 0;
+    if (pair_py > 0 &&
+        (st = dbuf_reserve(ix->ws_qimage,
+                           (size_t)dg_scan_qimage_bytes(nq, (int32_t)d),
+                           ix->stream, false)) != DG_OK) {
+      return st;
+    }
     if (fused) {
       if ((st = dbuf_reserve(ix->ws_partial,
                              (size_t)std::max<int64_t>(nq * partial_per_q, 1) *
@@ -2166,7 +2189,9 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                            (const float*)ix->d_csr_vnorms.p, dq, d,
                            inv_offsets32, inv_q, inv_rank, np, metric,
                            d_bitmap, chunk_rows, k, ix->cpl_max,
-                           (uint64_t*)ix->ws_partial.p, mfma);
+                           (uint64_t*)ix->ws_partial.p, mfma, nq,
+                           pair_py > 0 ? (float*)ix->ws_qimage.p : nullptr,
+                           pair_py);
       else
         dgk::ivf_scan_col(ix->stream, units, total_units,
                           (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
@@ -2296,9 +2321,11 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
     const size_t ids_bytes = (size_t)nq * k * 8;
     const bool fused_now = scan_fused_enabled();  // captured into the graph
     const bool mfma_now = scan_mfma_enabled();    // likewise
+    const int32_t pair_now = scan_pair_py();      // likewise
     if (ix->graph_exec && ix->graph_nq == (int32_t)nq &&
         ix->graph_k == k && ix->graph_np == nprobe &&
         ix->graph_fused == fused_now && ix->graph_mfma == mfma_now &&
+        ix->graph_pair == pair_now &&
         ix->graph_gen == gen) {
       DG_HIP_CHECK(hipMemcpyAsync(ix->ws_gq.p, d_x, q_bytes,
                                   hipMemcpyDeviceToDevice, ix->stream));
@@ -2353,6 +2380,7 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
           ix->graph_np = nprobe;
           ix->graph_fused = fused_now;
           ix->graph_mfma = mfma_now;
+          ix->graph_pair = pair_now;
           // capture itself allocates nothing (warm run sized buffers),
           // so gen2 still describes the captured pointers
           ix->graph_gen = gen2;
@@ -2819,6 +2847,12 @@ extern "C" int dg_last_scan_fused(dg_index* ix) {
   if (!ix) return 0;
   std::lock_guard sg(ix->search_mu);
   return ix->last_scan_fused ? 1 : 0;
+}
+
+extern "C" int dg_last_scan_pair(dg_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard sg(ix->search_mu);
+  return ix->last_scan_pair ? 1 : 0;
 }
 
 extern "C" int dg_last_scan_mfma(dg_index* ix) {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/dingo_gpu.h"
+#include "dg_scan_split.h"
 
 #define DG_HIP_CHECK(expr)                                              \
   do {                                                                  \
@@ -169,6 +170,9 @@ struct dg_index {
   // k <= kScanFuseMaxK (one result lane per rank, so at most 64); larger k
   // stores every candidate (DESIGN.md §Kernels has the measurement)
   static constexpr int32_t kScanFuseMaxK = 64;
+  // grid.y of the pair scan: a list's tile pairs are strided over it
+  // (DESIGN.md §Pair scan has the measurement)
+  static constexpr int32_t kScanPairPY = 2;
   int32_t cpl_max = 0;      // 1024-row chunks of the longest list
 
   // Flat uses d_csr_* with a single implicit list (nlist=1) so scan/select
@@ -210,6 +214,8 @@ struct dg_index {
   dg_dbuf ws_partial;
   bool last_scan_fused = false;  // path of the last search_core IVF scan
   bool last_scan_mfma = false;   // ... and whether it was k_ivf_scan_mfma
+  bool last_scan_pair = false;   // ... and whether k_ivf_scan_mfma2 ran too
+  dg_dbuf ws_qimage;             // its operand image of the queries
 
   // timing
   hipEvent_t ev[12] = {};
@@ -224,6 +230,7 @@ struct dg_index {
   int32_t graph_nq = 0, graph_k = 0, graph_np = 0;
   bool graph_fused = false;  // DG_SCAN_FUSED state the graph was captured in
   bool graph_mfma = false;   // DG_SCAN_MFMA state, likewise
+  int32_t graph_pair = 0;    // DG_SCAN_PAIR state, likewise
   uint64_t graph_gen = 0;   // generation the graph was captured at
   uint64_t index_gen = 1;   // bumped on finalize/mutation/buffer growth
   dg_dbuf ws_gq, ws_gout;   // fixed staging: queries in, dist+ids out
@@ -353,7 +360,10 @@ void ivf_scan_col(hipStream_t s, const uint32_t* units, int32_t n_units,
 // partial[nq][nprobe][cpl_max][chunk_rows/256][k]; the caller presets
 // partial to 0xff bytes (empty) and merges it with select_u64.  mfma picks
 // k_ivf_scan_mfma (f32 MFMA dots) over k_ivf_scan_pipe (VALU dots); both
-// fill the slots with the same bits.
+// fill the slots with the same bits.  With mfma, a non-null qimage
+// (dg_scan_qimage_bytes(nq, d) bytes of workspace) and
+// dg_scan_pair_applies(d, nq), lists probed by 17+ queries are scanned two
+// query tiles per pass by k_ivf_scan_mfma2 on a (units, pair_py) grid.
 void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                    const int64_t* csr_offsets, const int32_t* chunk_off,
                    const int64_t* chunk_base, const float* tvec,
@@ -361,7 +371,8 @@ void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                    const int32_t* inv_offsets, const int32_t* inv_q,
                    const int32_t* inv_rank, int32_t nprobe, int metric,
                    const uint32_t* bitmap, int32_t chunk_rows, int32_t k,
-                   int32_t cpl_max, uint64_t* partial, bool mfma);
+                   int32_t cpl_max, uint64_t* partial, bool mfma,
+                   int64_t nq, float* qimage, int32_t pair_py);
 void transpose_chunks(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int64_t* csr_offsets, const int32_t* chunk_off,
                       const int64_t* chunk_base, const float* rowmajor,

@@ -1757,7 +1757,8 @@ __global__ void __launch_bounds__(256, 3) k_ivf_scan_mfma(
     const int32_t* __restrict__ inv_offsets, const int32_t* __restrict__ inv_q,
     const int32_t* __restrict__ inv_rank, int32_t nprobe, int metric,
     const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
-    uint64_t* __restrict__ partial, int32_t kf, int32_t cpl_max) {
+    uint64_t* __restrict__ partial, int32_t kf, int32_t cpl_max,
+    int32_t pairing) {
   static_assert(QTM <= 16 && QTM % 4 == 0, "one 16-query MFMA tile");
   // [nper][QTM][4][4] floats, then cbase[QTM]
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1785,7 +1786,10 @@ __global__ void __launch_bounds__(256, 3) k_ivf_scan_mfma(
   // so 32 bits hold every byte offset into it
   const uint32_t kstepb = (uint32_t)nrows_pad * 16u;
 
-  for (int32_t t0 = 0; t0 < nql; t0 += QTM) {
+  // with pairing on (QTM 16 only) k_ivf_scan_mfma2 has taken the list's
+  // tile pairs: what is left is the odd last tile, or nothing
+  for (int32_t t0 = kScanTileQ * dg_scan_single_first(nql, pairing != 0);
+       t0 < nql; t0 += QTM) {
     const int32_t qt = min(QTM, nql - t0);
     __syncthreads();
     // float4 t of query j holds dims 4t..4t+3 = 16kb + 4s + g for g = 0..3
@@ -1927,6 +1931,203 @@ __global__ void __launch_bounds__(256, 3) k_ivf_scan_mfma(
       }
       dg_scan_topk_epilogue_mfma(acc, cbase, wslot, vnorms, nrows, rb, row0,
                                  qt, metric, bitmap, kf, partial);
+    }
+  }
+}
+
+// ---------- pair scan: two query tiles per pass over a chunk's rows ------
+// A list probed by more than 16 queries costs k_ivf_scan_mfma one HBM pass
+// over its chunk per 16-query tile.  k_ivf_scan_mfma2 feeds each k-step's
+// four row loads to 32 MFMAs, into one accumulator set per tile of a pair
+// (tiles 2p and 2p+1 of the list's probing queries), and runs the epilogue
+// once per set; dg_scan_split.h says which tiles it takes and which stay
+// with k_ivf_scan_mfma.  Every (query, row) dot is the same k-ordered chain
+// and every slot gets the same bits as from k_ivf_scan_mfma.
+//
+// A 32-query LDS image would leave one block per CU, so the A operand comes
+// from global memory: k_query_image writes every query once in the operand
+// order of the LDS image, [q][d/16 period][g 4][s 4] for dim 16kb+4s+g
+// (absent dims zero), plus one all-zero query at index nq for the absent
+// queries of a partial second tile.  Lane (g,i) loads its float4 of tile t
+// from image[inv_q[..16t+i]] one period ahead, in the row loads' pipeline.
+__global__ void k_query_image(const float* __restrict__ queries, int64_t nq,
+                              int32_t d, float* __restrict__ image) {
+  const int32_t nks = d >> 2;
+  const int32_t nf4 = ((nks + 3) >> 2) * 4;  // float4s per query image
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (nq + 1) * nf4) return;
+  const int64_t q = idx / nf4;
+  const int32_t t = (int32_t)(idx - q * nf4);
+  float4 v = float4{0.f, 0.f, 0.f, 0.f};
+  if (q < nq && t < nks) v = ((const float4*)(queries + (size_t)q * d))[t];
+  float* dst = image + ((size_t)q * nf4 + (t & ~3)) * 4 + (t & 3);
+  dst[0] = v.x;
+  dst[4] = v.y;
+  dst[8] = v.z;
+  dst[12] = v.w;
+}
+
+// SHORT is d <= 16, a single period: the instance for longer rows knows
+// that its dim loop runs at least once, so the accumulators have one
+// definition at the loop head instead of a merge with the zero-trip path
+// (which the register allocator resolves through scratch).
+template <bool SHORT>
+__global__ void __launch_bounds__(256, 2) k_ivf_scan_mfma2(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const float* __restrict__ tvec, const float* __restrict__ vnorms,
+    const float* __restrict__ image, int32_t zero_q, int32_t d,
+    const int32_t* __restrict__ inv_offsets, const int32_t* __restrict__ inv_q,
+    const int32_t* __restrict__ inv_rank, int32_t nprobe, int metric,
+    const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
+    uint64_t* __restrict__ partial, int32_t kf, int32_t cpl_max) {
+  constexpr int QT = kScanTileQ;
+  __shared__ int64_t cbase[2 * QT];
+  __builtin_assume(d % 4 == 0 && d > 0);
+  const int32_t nks = d >> 2;           // k-steps of 4 dims
+  const int32_t nper = (nks + 3) >> 2;  // periods of 4 k-steps
+
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int32_t iq0 = inv_offsets[list];
+  const int32_t nql = inv_offsets[list + 1] - iq0;
+  // blockIdx.y strides over the list's pairs; most units have none
+  const int32_t npairs = dg_scan_pairs(nql, true);
+  if ((int32_t)blockIdx.y >= npairs) return;
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t nrows_pad = (nrows + 3) & ~3;
+  const float* col = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+  const int64_t row0 = list_start + (int64_t)chunk * chunk_rows;
+
+  const int wave_id =
+      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const uint32_t kstepb = (uint32_t)nrows_pad * 16u;
+  // bytes per query image; the host launches this kernel only when the
+  // whole image (nq + 1 queries) is below 4 GiB
+  const uint32_t qimgb = (uint32_t)nper * 64u;
+
+  for (int32_t p = (int32_t)blockIdx.y; p < npairs; p += (int32_t)gridDim.y) {
+    const int32_t t0 = 2 * QT * p;
+    // tile 2p is whole; tile 2p+1 holds 1..16 queries
+    const int32_t qt1 = min(QT, nql - t0 - QT);
+    __syncthreads();
+    {
+      const int tid = wave_id * WAVE + dg_lane_id_fresh();
+      if (tid < 2 * QT) {
+        int64_t cb = 0;
+        if (tid < QT + qt1)
+          cb = ((((int64_t)inv_q[iq0 + t0 + tid] * nprobe +
+                  inv_rank[iq0 + t0 + tid]) * cpl_max + chunk) *
+                (chunk_rows / (WAVE * 4))) * kf;
+        cbase[tid] = cb;
+      }
+    }
+    __syncthreads();
+
+    for (int32_t rb = wave_id * WAVE * 4; rb < nrows_pad; rb += 4 * WAVE * 4) {
+      const int64_t wslot = (int64_t)(rb / (WAVE * 4)) * kf;
+      const int lane = dg_lane_id_fresh();
+      const int g = lane >> 4, i = lane & 15;
+      uint32_t voff[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const int32_t rr = rb + 64 * m + 4 * i;
+        voff[m] = ((uint32_t)g * (uint32_t)nrows_pad +
+                   (uint32_t)(rr < nrows_pad ? rr : 0)) * 4u;
+      }
+      // byte offsets of the lane's operand rows in the two queries' images;
+      // absent queries of the second tile read the zero query
+      const uint32_t aoff0 =
+          (uint32_t)inv_q[iq0 + t0 + i] * qimgb + (uint32_t)g * 16u;
+      const uint32_t aoff1 =
+          (uint32_t)(i < qt1 ? inv_q[iq0 + t0 + QT + i] : zero_q) * qimgb +
+          (uint32_t)g * 16u;
+
+      float z = 0.f;
+      asm volatile("" : "+v"(z));
+      dg_acc4 acc0[4][4], acc1[4][4];
+#pragma unroll
+      for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+          acc0[m][x] = dg_acc4{z, z, z, z};
+          acc1[m][x] = dg_acc4{z, z, z, z};
+        }
+      dg_acc4 b0[4], b1[4], b2[4], b3[4];
+      dg_acc4 a0, a1, n0, n1;  // this period's operands, the next period's
+      auto issue = [&](dg_acc4 (&b)[4], int32_t ks) {
+        const uint32_t uo =
+            __builtin_amdgcn_readfirstlane((uint32_t)ks * kstepb);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+          b[m] = *(const dg_acc4*)((const char*)col + (voff[m] + uo));
+      };
+      auto aissue = [&](dg_acc4& x0, dg_acc4& x1, int32_t per) {
+        const uint32_t po =
+            __builtin_amdgcn_readfirstlane((uint32_t)per * 64u);
+        x0 = *(const dg_acc4*)((const char*)image + (aoff0 + po));
+        x1 = *(const dg_acc4*)((const char*)image + (aoff1 + po));
+      };
+      auto compute = [&](const dg_acc4 (&b)[4], float x0, float x1) {
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+#pragma unroll
+          for (int x = 0; x < 4; x++) {
+            acc0[m][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                x0, b[m][x], acc0[m][x], 0, 0, 0);
+            acc1[m][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                x1, b[m][x], acc1[m][x], 0, 0, 0);
+          }
+      };
+
+      // the modulo schedule of k_ivf_scan_mfma; the next period's operands
+      // are issued just ahead of stage 0's re-issue, so the wait for that
+      // stage at the next period's head covers them
+      aissue(a0, a1, 0);
+      issue(b0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b1, min(1, nks - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b2, min(2, nks - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b3, min(3, nks - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      int32_t ks = 0;
+      if (!SHORT) __builtin_assume(nks > 4);
+      // (one loop form for every period that has a successor: where the
+      // successor has 1..3 k-steps its absent stages re-read the last
+      // column, as in the prologue, and are never consumed)
+      for (; !SHORT && ks + 4 < nks; ks += 4) {
+        compute(b0, a0.x, a1.x);
+        __builtin_amdgcn_sched_barrier(0);
+        aissue(n0, n1, (ks >> 2) + 1);
+        issue(b0, ks + 4);
+        compute(b1, a0.y, a1.y);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b1, min(ks + 5, nks - 1));
+        compute(b2, a0.z, a1.z);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b2, min(ks + 6, nks - 1));
+        compute(b3, a0.w, a1.w);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b3, min(ks + 7, nks - 1));
+        a0 = n0;
+        a1 = n1;
+      }
+      {  // last period: 1..4 k-steps; absent steps are skipped, not padded
+        const int32_t rem = nks - ks;
+        compute(b0, a0.x, a1.x);
+        if (rem > 1) compute(b1, a0.y, a1.y);
+        if (rem > 2) compute(b2, a0.z, a1.z);
+        if (rem > 3) compute(b3, a0.w, a1.w);
+      }
+      dg_scan_topk_epilogue_mfma(acc0, cbase, wslot, vnorms, nrows, rb, row0,
+                                 QT, metric, bitmap, kf, partial);
+      dg_scan_topk_epilogue_mfma(acc1, cbase + QT, wslot, vnorms, nrows, rb,
+                                 row0, qt1, metric, bitmap, kf, partial);
     }
   }
 }
@@ -3422,9 +3623,29 @@ void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                    const int32_t* inv_offsets, const int32_t* inv_q,
                    const int32_t* inv_rank, int32_t nprobe, int metric,
                    const uint32_t* bitmap, int32_t chunk_rows, int32_t k,
-                   int32_t cpl_max, uint64_t* partial, bool mfma) {
+                   int32_t cpl_max, uint64_t* partial, bool mfma,
+                   int64_t nq, float* qimage, int32_t pair_py) {
   if (!n_units) return;
   if (mfma) {
+    // pair scan first (the heavy units), then the tiles it leaves
+    const int32_t pairing = qimage && dg_scan_pair_applies(d, nq) ? 1 : 0;
+    if (pairing) {
+      const int64_t nf4 = (int64_t)((d + 15) / 16) * 4 * (nq + 1);
+      hipLaunchKernelGGL(k_query_image, dim3((uint32_t)((nf4 + 255) / 256)),
+                         dim3(256), 0, s, queries, nq, d, qimage);
+#define DG_PAIR_LAUNCH(SHORT)                                               \
+  hipLaunchKernelGGL((k_ivf_scan_mfma2<(SHORT)>),                           \
+                     dim3((uint32_t)n_units, (uint32_t)pair_py), dim3(256), \
+                     0, s, units, csr_offsets, chunk_off, chunk_base, tvec, \
+                     vnorms, qimage, (int32_t)nq, d, inv_offsets, inv_q,    \
+                     inv_rank, nprobe, metric, bitmap, chunk_rows, partial, \
+                     k, cpl_max)
+      if (d <= 16)
+        DG_PAIR_LAUNCH(true);
+      else
+        DG_PAIR_LAUNCH(false);
+#undef DG_PAIR_LAUNCH
+    }
     // same tile ladder; the LDS image is padded to whole 16-dim periods
 #define DG_MFMA_LAUNCH(QTM)                                                 \
   do {                                                                      \
@@ -3433,7 +3654,7 @@ void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
                        dim3(256), lds, s, units, csr_offsets, chunk_off,    \
                        chunk_base, tvec, vnorms, queries, d, inv_offsets,   \
                        inv_q, inv_rank, nprobe, metric, bitmap, chunk_rows, \
-                       partial, k, cpl_max);                                \
+                       partial, k, cpl_max, pairing);                       \
   } while (0)
     if (d <= 2304)
       DG_MFMA_LAUNCH(16);

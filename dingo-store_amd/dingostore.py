@@ -592,6 +592,15 @@ class Index:
         l.dg_last_scan_mfma.restype = C.c_int
         return bool(l.dg_last_scan_mfma(self.h))
 
+    def last_scan_pair(self):
+        """True if the last search also launched the pair scan (two query
+        tiles per pass on lists probed by 17+ queries); False with
+        DG_SCAN_PAIR=0, nq <= 16, d > 2304 or without the MFMA scan."""
+        l = lib()
+        l.dg_last_scan_pair.argtypes = [C.c_void_p]
+        l.dg_last_scan_pair.restype = C.c_int
+        return bool(l.dg_last_scan_pair(self.h))
+
     def stats(self):
         s = _Stats()
         _check(lib().dg_stats(self.h, C.byref(s)), "dg_stats")

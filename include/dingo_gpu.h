@@ -553,6 +553,12 @@ int dg_last_scan_fused(dg_index* idx);
 /* 1 if that fused scan ran the f32-MFMA kernel (the default), 0 if it ran
  * the VALU kernel (DG_SCAN_MFMA=0) or the search was not fused at all. */
 int dg_last_scan_mfma(dg_index* idx);
+
+/* 1 if the last search also launched the pair scan (k_ivf_scan_mfma2: lists
+ * probed by 17 or more queries are scanned two 16-query tiles per pass), 0
+ * if k_ivf_scan_mfma took every tile: DG_SCAN_PAIR=0, no more than 16
+ * queries, d > 2304, or not the f32-MFMA scan at all. */
+int dg_last_scan_pair(dg_index* idx);
 int dg_device_count(void);
 /* Library self-identification: returns a static string with build arch. */
 const char* dg_build_info(void);
