@@ -106,6 +106,21 @@ static int32_t scan_pair_py() {
   return dg_index::kScanPairPY;
 }
 
+// grid.y of k_ivf_scan_f16: the 16-query tiles of a list are strided over
+// it, so the block of a list probed by many queries does not run all of its
+// tiles in sequence.  One block row per 8 mean probes of a list (mean_probes
+// = nq * nprobe / nlist; the busiest lists have several times the mean), at
+// most 4: 1 at cfg C (8 probes per list), 4 at 32 (DESIGN.md §f16 row
+// storage has the measurement).  DG_SCAN_F16_PY = 1, 2 or 4 overrides it
+// (A/B switch, read per call; a graph replay keeps what it captured).
+static int32_t scan_f16_py(int32_t mean_probes) {
+  const char* e = getenv("DG_SCAN_F16_PY");
+  if (e && e[0] && e[1] == '\0' &&
+      (e[0] == '1' || e[0] == '2' || e[0] == '4'))
+    return e[0] - '0';
+  return std::min(4, std::max(1, (mean_probes + 7) / 8));
+}
+
 // Blocks per launch of the binary Flat range kernel; more columns than that
 // covers are scanned in several launches.  DG_RANGE_SPAN_BLOCKS lowers it
 // so that tests reach the multi-launch path at small sizes (read per call).
@@ -1136,10 +1151,11 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
     return DG_ENOT_TRAINED;
   }
   dg_status st = DG_OK;
+  const bool is_f16 = ix->storage == DG_STORAGE_F16;
   if (!is_pq && !ix->is_bin)  // PQ never keeps raw vectors (cfg D: 100M x
                               // 768 > HBM); binary keeps packed words
-    st = dbuf_reserve(ix->d_vectors, (size_t)(n0 + n) * d * 4, ix->stream,
-                      true);
+    st = dbuf_reserve(ix->d_vectors, (size_t)(n0 + n) * d * ix->elem_bytes(),
+                      ix->stream, true);
   if (st == DG_OK)
     st = dbuf_reserve(ix->d_ids, (size_t)(n0 + n) * 8, ix->stream, true);
   if (st == DG_OK)
@@ -1175,9 +1191,11 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   }
   dg_dbuf staging{};
   float* dst;
-  if (is_pq) {  // stage the incoming chunk (never mutate the caller's)
-    if ((st = dbuf_reserve(staging, (size_t)n * d * 4, ix->stream, false)) !=
-        DG_OK)
+  if (is_pq || is_f16) {  // stage the incoming chunk (never mutate the
+    // caller's); f16 storage assigns from the f32 staging (+ 4 bytes: the
+    // overflow flag of the conversion) and then stores the halves
+    if ((st = dbuf_reserve(staging, (size_t)n * d * 4 + 4, ix->stream,
+                           false)) != DG_OK)
       return st;
     dst = (float*)staging.p;
   } else {
@@ -1205,8 +1223,28 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
       return st;
     }
   }
-  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  int32_t h_overflow = 0;
+  if (is_f16) {
+    int32_t* d_flag = (int32_t*)((char*)staging.p + (size_t)n * d * 4);
+    (void)hipMemsetAsync(d_flag, 0, 4, ix->stream);
+    dgk::f32_to_f16_check(ix->stream, dst, (int64_t)n * d,
+                          (__half*)ix->d_vectors.p + (size_t)n0 * d, d_flag);
+    (void)hipMemcpyAsync(&h_overflow, d_flag, 4, hipMemcpyDeviceToHost,
+                         ix->stream);
+  }
+  {
+    const hipError_t e = hipStreamSynchronize(ix->stream);
+    if (e != hipSuccess) {
+      dbuf_free(staging);
+      DG_HIP_CHECK(e);
+    }
+  }
   dbuf_free(staging);
+  if (h_overflow) {  // nothing was appended: ntotal is unchanged
+    dg_set_error("%s: a component is NaN or exceeds the largest finite "
+                 "half (65504); DG_STORAGE_F16 cannot store it", fn);
+    return DG_EINVAL;
+  }
   for (int64_t i = 0; i < n; i++) ix->id_count.emplace(ids[i], 1);
   ix->ntotal += n;
   ix->csr_valid = false;
@@ -1367,6 +1405,128 @@ bool dg_contains_id(dg_index* ix, int64_t id) {
   return ix->id_count.count(id) != 0;
 }
 
+// ---------------- row storage ----------------
+extern "C" dg_status dg_set_storage(dg_index* ix, int32_t storage) {
+  if (!ix || (storage != DG_STORAGE_F32 && storage != DG_STORAGE_F16)) {
+    dg_set_error("bad dg_set_storage args");
+    return DG_EINVAL;
+  }
+  std::unique_lock lk(ix->rw);
+  if (ix->is_bin) {
+    dg_set_error("dg_set_storage: binary indexes store packed bits");
+    return DG_EINVAL;
+  }
+  if (storage == DG_STORAGE_F16 && ix->desc.kind != DG_INDEX_IVF_FLAT) {
+    dg_set_error("DG_STORAGE_F16 is implemented for DG_INDEX_IVF_FLAT only");
+    return DG_ENOT_SUPPORT;
+  }
+  if (ix->ntotal != 0) {
+    dg_set_error("dg_set_storage: the index already holds rows");
+    return DG_EINVAL;
+  }
+  if (ix->storage != storage) {
+    // the arrival store may have been reserved at create (desc.reserve) for
+    // the other component size; it is empty, so re-reserve it for the same
+    // number of rows (a buffer never shrinks by itself)
+    if (ix->d_vectors.cap > 0) {
+      DeviceGuard g(ix->device);
+      const size_t rows =
+          ix->d_vectors.cap / ((size_t)ix->desc.d * ix->elem_bytes());
+      (void)hipStreamSynchronize(ix->stream);
+      dbuf_free(ix->d_vectors);
+      ix->storage = storage;
+      const dg_status st = dbuf_reserve(
+          ix->d_vectors, rows * ix->desc.d * ix->elem_bytes(), ix->stream,
+          false);
+      if (st != DG_OK) return st;
+    }
+    ix->storage = storage;
+    ix->csr_valid = false;
+    ix->index_gen++;
+  }
+  return DG_OK;
+}
+
+extern "C" int32_t dg_get_storage(dg_index* ix) {
+  if (!ix) return -1;
+  std::shared_lock lk(ix->rw);
+  return ix->storage;
+}
+
+extern "C" int dg_last_scan_f16(dg_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard sg(ix->search_mu);
+  return ix->last_scan_f16 ? 1 : 0;
+}
+
+extern "C" dg_status dg_reconstruct(dg_index* ix, int64_t n,
+                                    const int64_t* ids, float* out) {
+  if (!ix || !ids || !out || n <= 0) {
+    dg_set_error("bad reconstruct args");
+    return DG_EINVAL;
+  }
+  if (ix->is_bin) {
+    dg_set_error("dg_reconstruct: binary index");
+    return DG_EINVAL;
+  }
+  if (ix->desc.kind == DG_INDEX_IVF_PQ) {
+    dg_set_error("dg_reconstruct: IVF-PQ keeps codes, not rows");
+    return DG_ENOT_SUPPORT;
+  }
+  std::shared_lock lk(ix->rw);
+  for (int64_t i = 0; i < n; i++)
+    if (!ix->id_count.count(ids[i])) {
+      dg_set_error("reconstruct not found vector id %lld",
+                   (long long)ids[i]);
+      return DG_ENOT_FOUND;
+    }
+  DeviceGuard g(ix->device);
+  // positions as dg_remove finds them: one download of the arrival ids
+  std::vector<int64_t> h_ids(ix->ntotal);
+  DG_HIP_CHECK(hipMemcpy(h_ids.data(), ix->d_ids.p, (size_t)ix->ntotal * 8,
+                         hipMemcpyDeviceToHost));
+  std::unordered_map<int64_t, int64_t> pos;
+  pos.reserve(n * 2);
+  for (int64_t i = 0; i < n; i++) pos.emplace(ids[i], -1);
+  for (int64_t i = 0; i < ix->ntotal; i++) {  // tombstones are negative ids
+    auto it = pos.find(h_ids[i]);
+    if (it != pos.end()) it->second = i;
+  }
+  std::vector<int64_t> plist(n);
+  for (int64_t i = 0; i < n; i++) {
+    plist[i] = pos[ids[i]];
+    if (plist[i] < 0) {
+      dg_set_error("reconstruct not found vector id %lld",
+                   (long long)ids[i]);
+      return DG_ENOT_FOUND;
+    }
+  }
+  const int32_t d = ix->desc.d;
+  // a private buffer keeps this call off the search workspaces; the stream
+  // is shared with the searches, hence search_mu around its use
+  dg_dbuf buf{};
+  DbufGuard bg(buf);
+  dg_status st =
+      dbuf_reserve(buf, (size_t)n * 8 + (size_t)n * d * 4, ix->stream, false);
+  if (st != DG_OK) return st;
+  int64_t* d_pos = (int64_t*)buf.p;
+  float* d_rows = (float*)((char*)buf.p + (size_t)n * 8);
+  std::lock_guard sg(ix->search_mu);
+  DG_HIP_CHECK(hipMemcpyAsync(d_pos, plist.data(), (size_t)n * 8,
+                              hipMemcpyHostToDevice, ix->stream));
+  if (ix->storage == DG_STORAGE_F16)
+    dgk::gather_rows_by_index_f16(ix->stream, (const __half*)ix->d_vectors.p,
+                                  d_pos, n, d, d_rows);
+  else
+    dgk::gather_rows_by_index(ix->stream, (const float*)ix->d_vectors.p,
+                              d_pos, n, d, d_rows);
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  DG_HIP_CHECK(hipMemcpy2D(out, (size_t)ix->d_user * 4, d_rows,
+                           (size_t)d * 4, (size_t)ix->d_user * 4, n,
+                           hipMemcpyDeviceToHost));
+  return DG_OK;
+}
+
 static dg_status upsert_impl(dg_index* ix, int64_t n, const int64_t* ids,
                              const void* x, bool binary_entry,
                              const char* fn) {
@@ -1375,6 +1535,25 @@ static dg_status upsert_impl(dg_index* ix, int64_t n, const int64_t* ids,
   std::vector<int64_t> existing;
   {
     std::shared_lock lk(ix->rw);
+    // f16 storage: the add below refuses a component no half can hold.
+    // Decide that here, on the caller's host rows, before anything is
+    // removed.  A non-finite value fails under every metric; a magnitude
+    // above 65504 only where the row is stored as given (the cosine
+    // normalisation brings every finite row to components of at most 1).
+    if (!binary_entry && ix->storage == DG_STORAGE_F16) {
+      const float* xf = (const float*)x;
+      const bool mag = ix->desc.metric != DG_METRIC_COSINE;
+      const int64_t cnt = n * (int64_t)ix->d_user;
+      for (int64_t i = 0; i < cnt; i++) {
+        const float v = xf[i];
+        if (!std::isfinite(v) || (mag && std::fabs(v) > 65504.0f)) {
+          dg_set_error("%s: a component is NaN or exceeds the largest "
+                       "finite half (65504); DG_STORAGE_F16 cannot store "
+                       "it; nothing was removed", fn);
+          return DG_EINVAL;
+        }
+      }
+    }
     for (int64_t i = 0; i < n; i++)
       if (ix->id_count.count(ids[i])) existing.push_back(ids[i]);
   }
@@ -1447,8 +1626,11 @@ static dg_status finalize_csr(dg_index* ix) {
                          (size_t)nlist * 4 + (size_t)n * 4 + 64, ix->stream,
                          false)) != DG_OK)
     return st;
+  // f16 storage (IVF-Flat only): rows, grouped rows and chunks are halves
+  const bool is_f16 = is_ivf && ix->storage == DG_STORAGE_F16;
+  const size_t eb = is_f16 ? 2 : 4;
   if (!is_pq &&
-      ((st = dbuf_reserve(rowmajor, (size_t)n * d * 4, ix->stream, false)) !=
+      ((st = dbuf_reserve(rowmajor, (size_t)n * d * eb, ix->stream, false)) !=
            DG_OK ||
        (!is_bin &&
         (st = dbuf_reserve(ix->d_csr_vnorms, (size_t)n * 4, ix->stream,
@@ -1488,6 +1670,11 @@ static dg_status finalize_csr(dg_index* ix) {
     } else if (is_bin) {  // word rows move as b_wp * 4 byte codes
       dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_codes.p, d_perm, n,
                         d * 4, (uint8_t*)rowmajor.p);
+    } else if (is_f16) {  // half rows move as d * 2 byte codes (d % 4 == 0)
+      dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_vectors.p, d_perm,
+                        n, d * 2, (uint8_t*)rowmajor.p);
+      dgk::row_norms_f16(ix->stream, (const __half*)rowmajor.p, n, d,
+                         (float*)ix->d_csr_vnorms.p);
     } else {
       dgk::gather_rows(ix->stream, (const float*)ix->d_vectors.p, d_perm, n,
                        d, (float*)rowmajor.p);
@@ -1534,7 +1721,8 @@ static dg_status finalize_csr(dg_index* ix) {
         chunk_base.push_back(t_elems);
         all_units.push_back((uint32_t)l);
         all_units.push_back((uint32_t)c);
-        t_elems += (int64_t)d * pad;
+        // f16 chunks pad the dims to 8 (zeros) and count halves
+        t_elems += (int64_t)(is_f16 ? (d + 7) & ~7 : d) * pad;
       }
     }
     ix->total_chunks = chunk_off[nlist];
@@ -1554,7 +1742,16 @@ static dg_status finalize_csr(dg_index* ix) {
       dbuf_free(rm_tmp);
       return st;
     }
-    if (is_ivf &&
+    if (is_f16 &&
+        // no slack: every load of k_ivf_scan_f16 falls inside its chunk
+        // (kernels.hip.cpp, f16 row storage); 64 bytes keep an empty
+        // buffer allocated
+        (st = dbuf_reserve(ix->d_csr_t, (size_t)t_elems * 2 + 64, ix->stream,
+                           false)) != DG_OK) {
+      dbuf_free(rm_tmp);
+      return st;
+    }
+    if (is_ivf && !is_f16 &&
         // slack past the last chunk: the glds scan's tail quarters issue
         // padded reads (d columns) and the asm-pipelined scan runs up to 15
         // columns ahead of d (last-iteration issue at base+31); results are
@@ -1580,7 +1777,12 @@ static dg_status finalize_csr(dg_index* ix) {
     (void)hipMemcpyAsync(d_all_units, all_units.data(),
                          (size_t)ix->total_chunks * 8, hipMemcpyHostToDevice,
                          ix->stream);
-    if (is_ivf)
+    if (is_f16)
+      dgk::transpose_chunks_f16(ix->stream, d_all_units, ix->total_chunks,
+                                d_offsets, d_chunk_off, d_chunk_base,
+                                (const __half*)rowmajor.p, d, CR,
+                                (__half*)ix->d_csr_t.p);
+    else if (is_ivf)
       dgk::transpose_chunks(ix->stream, d_all_units, ix->total_chunks,
                             d_offsets, d_chunk_off, d_chunk_base,
                             (const float*)rowmajor.p, d, CR,
@@ -2077,11 +2279,17 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                        k <= dg_index::kScanFuseMaxK &&
                        nq * partial_per_q <= ub_cand && scan_fused_enabled();
     ix->last_scan_fused = fused;
-    const bool mfma = fused && scan_mfma_enabled();
+    // f16 row storage: k_ivf_scan_f16 serves both candidate flows (always
+    // the MFMA body, no pair scan)
+    const bool is_f16 = !is_pq && !is_bin && ix->storage == DG_STORAGE_F16;
+    ix->last_scan_f16 = is_f16;
+    const bool mfma = fused && (is_f16 || scan_mfma_enabled());
     ix->last_scan_mfma = mfma;
     // lists probed by 17+ queries: two query tiles per pass over the rows
     const int32_t pair_py =
-        mfma && dg_scan_pair_applies((int32_t)d, nq) ? scan_pair_py() : 0;
+        mfma && !is_f16 && dg_scan_pair_applies((int32_t)d, nq)
+            ? scan_pair_py()
+            : 0;
     ix->last_scan_pair = pair_py > 0;
     if (pair_py > 0 &&
         (st = dbuf_reserve(ix->ws_qimage,
@@ -2117,6 +2325,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     // pinned memory; dg_stats synchronizes on ev[5]
     const int64_t row_bytes = is_pq    ? dg_pq_code_size(ix->desc)
                               : is_bin ? (int64_t)(ix->d_user / 8)
+                              : is_f16 ? (int64_t)(d * 2 + 4)
                                        : (int64_t)(d * 4 + 4);
     if (ix->h_pinned && !ix->capturing) {
       dg_dbuf& wsu = ix->ws_units;
@@ -2182,6 +2391,17 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                        (const uint32_t*)dq, d, inv_offsets32, inv_q, inv_rank,
                        qp_off, q_cand_base, np, d_bitmap, chunk_rows,
                        (uint64_t*)ix->ws_cand.p);
+      else if (is_f16)
+        dgk::ivf_scan_f16(ix->stream, units, total_units,
+                          (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
+                          d_chunk_base, (const __half*)ix->d_csr_t.p,
+                          (const float*)ix->d_csr_vnorms.p, dq, d,
+                          inv_offsets32, inv_q, inv_rank, qp_off, q_cand_base,
+                          np, metric, d_bitmap, chunk_rows, fused, k,
+                          ix->cpl_max,
+                          (uint64_t*)(fused ? ix->ws_partial.p
+                                            : ix->ws_cand.p),
+                          scan_f16_py(mean_probes));
       else if (fused)
         dgk::ivf_scan_topk(ix->stream, units, total_units,
                            (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
@@ -2614,6 +2834,9 @@ extern "C" void dg_free(void* p) { free(p); }
 
 // ---------------- save / load (container v1) ----------------
 static const uint32_t kMagic = 0x44474931;  // "DGI1"
+// "DGI2": DGI1 with an int32 dg_storage word after the magic; written only
+// for a storage other than f32, so an f32 container stays byte for byte DGI1
+static const uint32_t kMagicStorage = 0x44474932;
 
 extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   if (!ix || !path) return DG_EINVAL;
@@ -2631,7 +2854,13 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   }
   const int32_t d = ix->desc.d;
   int32_t trained = ix->trained ? 1 : 0;
-  fwrite(&kMagic, 4, 1, f);
+  const bool is_f16 = ix->storage == DG_STORAGE_F16;
+  if (is_f16) {  // "DGI2": a storage word follows the magic, rows are halves
+    fwrite(&kMagicStorage, 4, 1, f);
+    fwrite(&ix->storage, 4, 1, f);
+  } else {
+    fwrite(&kMagic, 4, 1, f);
+  }
   dg_index_desc udesc = ix->desc;
   udesc.d = ix->d_user;  // container speaks the caller's dimension
   fwrite(&udesc, sizeof(udesc), 1, f);
@@ -2671,6 +2900,13 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
                       c * M, hipMemcpyDeviceToHost) != hipSuccess)
           st = DG_EINTERNAL;
         fwrite(cbuf.data(), 1, c * M, f);
+      } else if (is_f16) {  // d_user halves per row, the pad stripped
+        if (hipMemcpy2D(vbuf.data(), (size_t)ix->d_user * 2,
+                        (const __half*)ix->d_vectors.p + (size_t)s0 * d,
+                        (size_t)d * 2, (size_t)ix->d_user * 2, c,
+                        hipMemcpyDeviceToHost) != hipSuccess)
+          st = DG_EINTERNAL;
+        fwrite(vbuf.data(), 2, c * ix->d_user, f);
       } else {
         if (download_rows_strip(ix, vbuf.data(),
                                 (float*)ix->d_vectors.p + (size_t)s0 * d,
@@ -2721,7 +2957,11 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
   dg_index_desc desc{};
   int32_t trained = 0;
   int64_t ntotal = 0, ndel = 0;
-  if (fread(&magic, 4, 1, f) != 1 || magic != kMagic ||
+  int32_t storage = DG_STORAGE_F32;
+  if (fread(&magic, 4, 1, f) != 1 ||
+      (magic != kMagic && magic != kMagicStorage) ||
+      (magic == kMagicStorage &&
+       (fread(&storage, 4, 1, f) != 1 || storage != DG_STORAGE_F16)) ||
       fread(&desc, sizeof(desc), 1, f) != 1 || fread(&trained, 4, 1, f) != 1 ||
       fread(&ntotal, 8, 1, f) != 1 || fread(&ndel, 8, 1, f) != 1) {
     fclose(f);
@@ -2738,7 +2978,9 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
   DeviceGuard g(ix->device);
   const int32_t d = desc.d;
   const bool is_pq = desc.kind == DG_INDEX_IVF_PQ;
+  const bool is_f16 = storage == DG_STORAGE_F16;
   do {
+    if (is_f16 && (st = dg_set_storage(ix, storage)) != DG_OK) break;
     if (desc.kind != DG_INDEX_FLAT && trained) {
       std::vector<float> cents((size_t)desc.nlist * d);
       if (fread(cents.data(), 4, cents.size(), f) != cents.size()) {
@@ -2767,9 +3009,11 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
                              false)) != DG_OK)
         break;
       if (!is_pq && (st = dbuf_reserve(ix->d_vectors,
-                                       (size_t)ntotal * dp * 4,
+                                       (size_t)ntotal * dp * ix->elem_bytes(),
                                        ix->stream, false)) != DG_OK)
         break;
+      if (is_f16 && dp != d)  // the pad columns are never written below
+        (void)hipMemset(ix->d_vectors.p, 0, (size_t)ntotal * dp * 2);
       if (is_pq && (st = dbuf_reserve(ix->d_codes, (size_t)ntotal * M,
                                       ix->stream, false)) != DG_OK)
         break;
@@ -2788,6 +3032,16 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
           if (hipMemcpy((uint8_t*)ix->d_codes.p + (size_t)s0 * M,
                         cbuf.data(), c * M,
                         hipMemcpyHostToDevice) != hipSuccess)
+            st = DG_EINTERNAL;
+        } else if (is_f16) {  // stored halves go back bit for bit
+          if (fread(vbuf.data(), 2, c * d, f) != c * d) {
+            st = DG_EIO;
+            break;
+          }
+          if (hipMemcpy2D((__half*)ix->d_vectors.p + (size_t)s0 * dp,
+                          (size_t)dp * 2, vbuf.data(), (size_t)d * 2,
+                          (size_t)d * 2, c,
+                          hipMemcpyHostToDevice) != hipSuccess)
             st = DG_EINTERNAL;
         } else {
           if (fread(vbuf.data(), 4, c * d, f) != c * d) {

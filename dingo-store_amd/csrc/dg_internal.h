@@ -139,7 +139,16 @@ struct dg_index {
   rocblas_handle blas = nullptr;
 
   // ---- store (arrival order; the base of truth) ----
-  dg_dbuf d_vectors;   // [ntotal x d] f32 (normalized already for cosine)
+  dg_dbuf d_vectors;   // [ntotal x d] f32 (normalized already for cosine);
+                       // halves when storage == DG_STORAGE_F16
+  // Row storage (dg_set_storage; IVF-Flat only).  It is not part of
+  // dg_index_desc, which dg_save writes raw.  With DG_STORAGE_F16 the
+  // arrival store and the chunks d_csr_t hold IEEE halves; centroids,
+  // assignment, queries and d_csr_vnorms (norms of the decoded rows) stay
+  // f32.
+  int32_t storage = DG_STORAGE_F32;
+  size_t elem_bytes() const { return storage == DG_STORAGE_F16 ? 2 : 4; }
+  bool last_scan_f16 = false;  // the last search_core scan was k_ivf_scan_f16
   dg_dbuf d_ids;       // [ntotal] i64
   dg_dbuf d_assign;    // [ntotal] i32 (IVF only; coarse list per vector)
   int64_t ntotal = 0;
@@ -377,6 +386,40 @@ void transpose_chunks(hipStream_t s, const uint32_t* units, int32_t n_units,
                       const int64_t* csr_offsets, const int32_t* chunk_off,
                       const int64_t* chunk_base, const float* rowmajor,
                       int32_t d, int32_t chunk_rows, float* tvec);
+// ---- f16 row storage (DG_STORAGE_F16, IVF-Flat) ----
+// out = round-to-nearest-even half of in; *overflow |= 1 if a component is
+// NaN or exceeds the largest finite half
+void f32_to_f16_check(hipStream_t s, const float* in, int64_t n, __half* out,
+                      int32_t* overflow);
+// squared norms of the decoded rows
+void row_norms_f16(hipStream_t s, const __half* x, int64_t n, int32_t d,
+                   float* out);
+// dst[i] = decoded row idx[i] of src (d halves per row, d floats out)
+void gather_rows_by_index_f16(hipStream_t s, const __half* src,
+                              const int64_t* idx, int64_t n, int32_t d,
+                              float* dst);
+// row-major halves -> the chunk layout k_ivf_scan_f16 reads (kernels.hip.cpp
+// documents it); chunk_base counts halves, a chunk is ceil(d/8)*8 x
+// ceil(nrows/4)*4 of them
+void transpose_chunks_f16(hipStream_t s, const uint32_t* units,
+                          int32_t n_units, const int64_t* csr_offsets,
+                          const int32_t* chunk_off, const int64_t* chunk_base,
+                          const __half* rowmajor, int32_t d,
+                          int32_t chunk_rows, __half* tvec);
+// the IVF-Flat scan over f16 chunks, one dot-product body for both candidate
+// flows: fused writes the per-wave top-k slots of ivf_scan_topk to out
+// (qp_off / q_cand_base unused), otherwise every candidate goes to out in
+// the layout of ivf_scan_col
+void ivf_scan_f16(hipStream_t s, const uint32_t* units, int32_t n_units,
+                  const int64_t* csr_offsets, const int32_t* chunk_off,
+                  const int64_t* chunk_base, const __half* tvec,
+                  const float* vnorms, const float* queries, int32_t d,
+                  const int32_t* inv_offsets, const int32_t* inv_q,
+                  const int32_t* inv_rank, const int64_t* qp_off,
+                  const int64_t* q_cand_base, int32_t nprobe, int metric,
+                  const uint32_t* bitmap, int32_t chunk_rows, bool fused,
+                  int32_t k, int32_t cpl_max, uint64_t* out,
+                  int32_t py /* grid.y: a list's tiles are strided over it */);
 // range search
 void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,
                 const int64_t* ids_lookup, const float* qnorms, int64_t nq,

@@ -534,6 +534,24 @@ extern "C" dg_index* dg_sharded_shard(dg_sharded* sh, int32_t i) {
   return sh && i >= 0 && i < sh->n ? sh->shards[i] : nullptr;
 }
 
+extern "C" dg_status dg_sharded_set_storage(dg_sharded* sh, int32_t storage) {
+  if (!sh) return DG_EINVAL;
+  std::unique_lock lk(sh->rw);
+  // all or none: a shard that already holds rows would refuse
+  for (dg_index* ix : sh->shards) {
+    std::shared_lock sl(ix->rw);
+    if (ix->ntotal != 0) {
+      dg_set_error("dg_sharded_set_storage: the index already holds rows");
+      return DG_EINVAL;
+    }
+  }
+  for (dg_index* ix : sh->shards) {
+    const dg_status st = dg_set_storage(ix, storage);
+    if (st != DG_OK) return st;
+  }
+  return DG_OK;
+}
+
 // ---------------- train / structure ----------------
 static dg_status replicate_from_shard0(dg_sharded* sh) {
   dg_index* s0 = sh->shards[0];

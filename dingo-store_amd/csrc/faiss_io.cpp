@@ -314,6 +314,12 @@ extern "C" dg_status dg_save_faiss(dg_index* ix, const char* path) {
     return DG_ENOT_SUPPORT;
   }
   std::shared_lock lk(ix->rw);
+  if (ix->storage != DG_STORAGE_F32) {
+    dg_set_error("dg_save_faiss: f16 row storage would need a scalar-"
+                 "quantiser file, which the CPU nodes' IndexIVFFlat loader "
+                 "cannot read: use dg_save");
+    return DG_ENOT_SUPPORT;
+  }
   DeviceGuard g{ix->device};
   const int32_t d = ix->d_user;  // containers speak the caller's dimension
   const int fm = to_faiss_metric(ix->desc.metric);

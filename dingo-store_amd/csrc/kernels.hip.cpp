@@ -1935,6 +1935,345 @@ __global__ void __launch_bounds__(256, 3) k_ivf_scan_mfma(
   }
 }
 
+// ---------- f16 row storage (DG_STORAGE_F16) ----------
+// Rows are stored as IEEE halves, the query stays f32.  k_ivf_scan_f16 is
+// k_ivf_scan_mfma with the halves decoded in registers: the same 16x16x4 f32
+// MFMA mapping, accumulator layout, row ownership and per-wave epilogue, so
+// a distance is the f32 k-ordered chain over the f32 query and the decoded
+// row (exact products: a half has 11 significant bits).
+//
+// Chunk layout, written by k_transpose_chunks_f16: with d8 = ceil(d/8)*8
+// (dims past d are zeros) and nrows_pad = ceil(nrows/4)*4 (rows past nrows
+// are zeros), a chunk is [d8/8 kp][4 g][nrows_pad/4 quads][2 h][4 x] halves
+// holding dim 8kp + 4h + g of row 4*quad + x.  A lane's 16-byte load at
+// ((4kp + g) * nrows_pad + row) * 4 bytes is the B operand (k = g) of the
+// k-steps 2kp (h = 0) and 2kp+1 (h = 1) for four consecutive rows: the byte
+// offsets are those of the f32 layout, each load feeding two k-steps.  A
+// chunk is d8 * nrows_pad halves, a multiple of 64 bytes.  Every load falls
+// inside the chunk (lanes past nrows_pad re-read its first quad, absent
+// prologue stages re-read its last kp), so the buffer needs no slack.
+typedef _Float16 dg_h8 __attribute__((ext_vector_type(8)));
+
+__global__ void k_f32_to_f16_check(const float* __restrict__ in, int64_t n,
+                                   __half* __restrict__ out,
+                                   int32_t* __restrict__ overflow) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float v = in[i];
+  if (!(fabsf(v) <= kHalfMax)) atomicOr(overflow, 1);  // NaN fails too
+  out[i] = __float2half_rn(v);
+}
+
+__global__ void k_row_norms_f16(const __half* __restrict__ x, int64_t n,
+                                int32_t d, float* __restrict__ out) {
+  const int64_t row = (int64_t)blockIdx.x * (blockDim.x / WAVE) +
+                      threadIdx.x / WAVE;
+  if (row >= n) return;
+  const int lane = threadIdx.x % WAVE;
+  const __half* p = x + (size_t)row * d;
+  float s = 0.f;
+  for (int32_t i = lane; i < d; i += WAVE) {
+    const float v = __half2float(p[i]);
+    s += v * v;
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off);
+  if (lane == 0) out[row] = s;
+}
+
+// out[i] = decoded row idx[i] of src, d_src halves per row, d floats out
+__global__ void k_gather_rows_by_index_f16(const __half* __restrict__ src,
+                                           const int64_t* __restrict__ idx,
+                                           int64_t n, int32_t d,
+                                           float* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * d) return;
+  const int64_t r = i / d;
+  const int32_t c = (int32_t)(i - r * d);
+  dst[i] = __half2float(src[(size_t)idx[r] * d + c]);
+}
+
+__global__ void __launch_bounds__(256) k_transpose_chunks_f16(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const __half* __restrict__ rowmajor, int32_t d, int32_t chunk_rows,
+    __half* __restrict__ tvec) {
+  __shared__ uint16_t tile[64][66];
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t nrows_pad = (nrows + 3) & ~3;
+  const int32_t d8 = (d + 7) & ~7;
+  const uint16_t* src = (const uint16_t*)rowmajor +
+                        (list_start + (int64_t)chunk * chunk_rows) * d;
+  uint16_t* dst =
+      (uint16_t*)tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+
+  const int tx = threadIdx.x % 64;
+  const int ty = threadIdx.x / 64;
+  for (int32_t r0 = 0; r0 < nrows_pad; r0 += 64) {
+    for (int32_t i0 = 0; i0 < d8; i0 += 64) {
+      __syncthreads();
+      for (int rr = ty; rr < 64; rr += 4) {
+        const int32_t r = r0 + rr;
+        tile[rr][tx] = (r < nrows && i0 + tx < d)
+                           ? src[(size_t)r * d + i0 + tx]
+                           : (uint16_t)0;
+      }
+      __syncthreads();
+      // 8 kp x 4 g x 16 quads = 512 16-byte groups per tile
+      for (int t = threadIdx.x; t < 512; t += 256) {
+        const int quad = t & 15, g = (t >> 4) & 3, kpl = t >> 6;
+        const int32_t kp = (i0 >> 3) + kpl;
+        const int32_t r = r0 + 4 * quad;
+        if (8 * kp < d8 && r < nrows_pad) {
+          uint32_t w[4];  // one 16-byte store: chunks are 64-byte aligned
+#pragma unroll
+          for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int x = 0; x < 4; x += 2)
+              w[2 * h + (x >> 1)] =
+                  (uint32_t)tile[4 * quad + x][8 * kpl + 4 * h + g] |
+                  ((uint32_t)tile[4 * quad + x + 1][8 * kpl + 4 * h + g]
+                   << 16);
+          *(uint4*)(dst + ((size_t)(4 * kp + g) * nrows_pad + r) * 2) =
+              make_uint4(w[0], w[1], w[2], w[3]);
+        }
+      }
+    }
+  }
+}
+
+// Store-all epilogue for the MFMA register layout: every (query, row) pair of
+// the wave's 256-row block goes to the dense candidate buffer
+// (cand[cbase[query] + chunk-local row], the layout of ivf_scan_col_body),
+// with the key expression of dg_scan_topk_epilogue_mfma.
+__device__ __forceinline__ void dg_scan_store_epilogue_mfma(
+    const dg_acc4 (&acc)[4][4], const int64_t* cbase,
+    const float* __restrict__ vnorms, int32_t nrows, int32_t rb, int64_t row0,
+    int32_t qt, int metric, const uint32_t* __restrict__ bitmap,
+    uint64_t* __restrict__ cand) {
+  const int lane = dg_lane_id_fresh();
+  const int g = lane >> 4, j = lane & 15;
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const int32_t rl = rb + 64 * (e >> 2) + 4 * j + (e & 3);
+    if (rl >= nrows) continue;
+    const int64_t r = row0 + rl;
+    bool pass = true;
+    if (bitmap) pass = (bitmap[r >> 5] >> (r & 31)) & 1;
+    const float vn = (metric == 0) ? vnorms[r] : 0.f;
+#pragma unroll
+    for (int rq = 0; rq < 4; rq++) {
+      const int jq = 4 * g + rq;
+      if (jq < qt) {
+        const float a = acc[e >> 2][e & 3][rq];
+        const float key = (metric == 0) ? vn - 2.0f * a : -a;
+        cand[cbase[jq] + rl] = pass ? pack_cand(key, (uint32_t)r) : kCandEmpty;
+      }
+    }
+  }
+}
+
+// FUSED: per-wave top-k into `out` (= partial, qp_off / q_cand_base unused);
+// otherwise every candidate into `out` (= cand).  One dot-product body.
+template <int QTM, bool FUSED>
+__global__ void __launch_bounds__(256, 2) k_ivf_scan_f16(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const __half* __restrict__ tvec, const float* __restrict__ vnorms,
+    const float* __restrict__ queries, int32_t d,
+    const int32_t* __restrict__ inv_offsets, const int32_t* __restrict__ inv_q,
+    const int32_t* __restrict__ inv_rank, const int64_t* __restrict__ qp_off,
+    const int64_t* __restrict__ q_cand_base, int32_t nprobe, int metric,
+    const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
+    uint64_t* __restrict__ out, int32_t kf, int32_t cpl_max) {
+  static_assert(QTM <= 16 && QTM % 4 == 0, "one 16-query MFMA tile");
+  // [nper][QTM][4][4] floats (nper even: whole 32-dim periods), cbase[QTM]
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __builtin_assume(d % 4 == 0 && d > 0);
+  const int32_t nf4 = d >> 2;             // float4s of a query
+  const int32_t nkp = (d + 7) >> 3;       // loads per lane and m: 8 dims each
+  const int32_t nper = ((nkp + 3) >> 2) * 2;  // 16-dim LDS periods
+  int64_t* cbase = (int64_t*)(smem + (size_t)nper * QTM * 16);
+
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t nrows_pad = (nrows + 3) & ~3;
+  const __half* col = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+  const int64_t row0 = list_start + (int64_t)chunk * chunk_rows;
+  const int32_t iq0 = inv_offsets[list];
+  const int32_t nql = inv_offsets[list + 1] - iq0;
+
+  const int wave_id =
+      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  // bytes per kp (8 dims x nrows_pad halves); a chunk is at most 8192 x 1024
+  // halves, so 32 bits hold every byte offset into it
+  const uint32_t kstepb = (uint32_t)nrows_pad * 16u;
+
+  // a list's query tiles are strided over grid.y, so that a list probed by
+  // many queries is not one block's serial work (DESIGN.md §f16 row
+  // storage has the measurement); tiles are independent, the slots and
+  // candidates of a query are written by its own tile alone
+  for (int32_t t0 = QTM * (int32_t)blockIdx.y; t0 < nql;
+       t0 += QTM * (int32_t)gridDim.y) {
+    const int32_t qt = min(QTM, nql - t0);
+    __syncthreads();
+    // the LDS image of k_ivf_scan_mfma: float4 t of query j holds dims
+    // 16kb + 4s + g (kb = t>>2, s = t&3); absent queries and dims are zero
+    const int tid = wave_id * WAVE + dg_lane_id_fresh();
+#pragma unroll 1
+    for (int32_t j = 0; j < QTM; j++) {
+      const float4* src =
+          j < qt ? (const float4*)(queries +
+                                   (size_t)inv_q[iq0 + t0 + j] * d)
+                 : nullptr;
+      for (int32_t t = tid; t < nper * 4; t += blockDim.x) {
+        float4 v = float4{0.f, 0.f, 0.f, 0.f};
+        if (src && t < nf4) v = src[t];
+        float* dst = smem + ((size_t)(t >> 2) * QTM + j) * 16 + (t & 3);
+        dst[0] = v.x;
+        dst[4] = v.y;
+        dst[8] = v.z;
+        dst[12] = v.w;
+      }
+    }
+    if (tid < QTM) {
+      const int32_t j = tid;
+      int64_t cb = 0;
+      if (j < qt) {
+        const int32_t q = inv_q[iq0 + t0 + j];
+        const int32_t rank = inv_rank[iq0 + t0 + j];
+        if (FUSED)
+          cb = ((((int64_t)q * nprobe + rank) * cpl_max + chunk) *
+                (chunk_rows / (WAVE * 4))) * kf;
+        else
+          cb = q_cand_base[q] + qp_off[(int64_t)q * nprobe + rank] +
+               (int64_t)chunk * chunk_rows;
+      }
+      cbase[j] = cb;
+    }
+    __syncthreads();
+
+    for (int32_t rb = wave_id * WAVE * 4; rb < nrows_pad; rb += 4 * WAVE * 4) {
+      const int lane = dg_lane_id_fresh();
+      const int g = lane >> 4, i = lane & 15;
+      uint32_t voff[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const int32_t rr = rb + 64 * m + 4 * i;
+        voff[m] = ((uint32_t)g * (uint32_t)nrows_pad +
+                   (uint32_t)(rr < nrows_pad ? rr : 0)) * 4u;
+      }
+      const dg_acc4* ap = (const dg_acc4*)smem + (i < QTM ? i : 0) * 4 + g;
+
+      float z = 0.f;
+      asm volatile("" : "+v"(z));
+      dg_acc4 acc[4][4];
+#pragma unroll
+      for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int x = 0; x < 4; x++) acc[m][x] = dg_acc4{z, z, z, z};
+      dg_h8 b0[4], b1[4], b2[4], b3[4];
+      auto issue = [&](dg_h8 (&b)[4], int32_t kp) {
+        const uint32_t uo =
+            __builtin_amdgcn_readfirstlane((uint32_t)kp * kstepb);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+          b[m] = *(const dg_h8*)((const char*)col + (voff[m] + uo));
+      };
+      // k-step 2kp (a0: dims 8kp + g) then 2kp+1 (a1: dims 8kp + 4 + g)
+      auto compute = [&](const dg_h8 (&b)[4], float a0, float a1) {
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+#pragma unroll
+          for (int x = 0; x < 4; x++)
+            acc[m][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                a0, (float)b[m][x], acc[m][x], 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+#pragma unroll
+          for (int x = 0; x < 4; x++)
+            acc[m][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                a1, (float)b[m][4 + x], acc[m][x], 0, 0, 0);
+      };
+      auto qload = [&]() {
+        dg_acc4 a = *ap;
+        ap += QTM * 4;
+        if (QTM < 16 && i >= QTM) a = dg_acc4{0.f, 0.f, 0.f, 0.f};
+        return a;
+      };
+
+      // modulo schedule as in k_ivf_scan_mfma; a stage is one kp (8 dims),
+      // a period four stages = 32 dims = two LDS reads
+      issue(b0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b1, min(1, nkp - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b2, min(2, nkp - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b3, min(3, nkp - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      int32_t kp = 0;
+      for (; kp + 8 <= nkp; kp += 4) {  // the next period is whole too
+        const dg_acc4 a = qload();
+        const dg_acc4 c = qload();
+        compute(b0, a.x, a.y);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b0, kp + 4);
+        compute(b1, a.z, a.w);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b1, kp + 5);
+        compute(b2, c.x, c.y);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b2, kp + 6);
+        compute(b3, c.z, c.w);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b3, kp + 7);
+      }
+      if (kp + 4 < nkp) {  // whole period followed by a 1..3-stage one
+        const int32_t rem = nkp - kp - 4;
+        const dg_acc4 a = qload();
+        const dg_acc4 c = qload();
+        compute(b0, a.x, a.y);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b0, kp + 4);
+        compute(b1, a.z, a.w);
+        __builtin_amdgcn_sched_barrier(0);
+        if (rem > 1) issue(b1, kp + 5);
+        compute(b2, c.x, c.y);
+        __builtin_amdgcn_sched_barrier(0);
+        if (rem > 2) issue(b2, kp + 6);
+        compute(b3, c.z, c.w);
+        kp += 4;
+      }
+      {  // last period: 1..4 stages; absent stages are skipped
+        const int32_t rem = nkp - kp;
+        const dg_acc4 a = qload();
+        const dg_acc4 c = qload();
+        compute(b0, a.x, a.y);
+        if (rem > 1) compute(b1, a.z, a.w);
+        if (rem > 2) compute(b2, c.x, c.y);
+        if (rem > 3) compute(b3, c.z, c.w);
+      }
+      if (FUSED)
+        dg_scan_topk_epilogue_mfma(acc, cbase,
+                                   (int64_t)(rb / (WAVE * 4)) * kf, vnorms,
+                                   nrows, rb, row0, qt, metric, bitmap, kf,
+                                   out);
+      else
+        dg_scan_store_epilogue_mfma(acc, cbase, vnorms, nrows, rb, row0, qt,
+                                    metric, bitmap, out);
+    }
+  }
+}
+
 // ---------- pair scan: two query tiles per pass over a chunk's rows ------
 // A list probed by more than 16 queries costs k_ivf_scan_mfma one HBM pass
 // over its chunk per 16-query tile.  k_ivf_scan_mfma2 feeds each k-step's
@@ -3683,6 +4022,79 @@ void ivf_scan_topk(hipStream_t s, const uint32_t* units, int32_t n_units,
   else
     DG_PIPE_LAUNCH(4);
 #undef DG_PIPE_LAUNCH
+}
+
+void ivf_scan_f16(hipStream_t s, const uint32_t* units, int32_t n_units,
+                  const int64_t* csr_offsets, const int32_t* chunk_off,
+                  const int64_t* chunk_base, const __half* tvec,
+                  const float* vnorms, const float* queries, int32_t d,
+                  const int32_t* inv_offsets, const int32_t* inv_q,
+                  const int32_t* inv_rank, const int64_t* qp_off,
+                  const int64_t* q_cand_base, int32_t nprobe, int metric,
+                  const uint32_t* bitmap, int32_t chunk_rows, bool fused,
+                  int32_t k, int32_t cpl_max, uint64_t* out, int32_t py) {
+  if (!n_units) return;
+  // the tile ladder of k_ivf_scan_mfma; the LDS image is padded to whole
+  // 32-dim periods
+#define DG_F16_LAUNCH(QTM, FUSED)                                           \
+  do {                                                                      \
+    size_t lds = (size_t)((d + 31) / 32) * 2 * (QTM) * 64 + (QTM) * 8;      \
+    hipLaunchKernelGGL((k_ivf_scan_f16<(QTM), (FUSED)>),                    \
+                       dim3((uint32_t)n_units, (uint32_t)py), dim3(256),    \
+                       lds, s, units, csr_offsets, chunk_off, chunk_base,   \
+                       tvec, vnorms, queries, d, inv_offsets, inv_q,        \
+                       inv_rank, qp_off, q_cand_base, nprobe, metric,       \
+                       bitmap, chunk_rows, out, k, cpl_max);                \
+  } while (0)
+#define DG_F16_LADDER(FUSED)                                                \
+  do {                                                                      \
+    if (d <= 2304)                                                          \
+      DG_F16_LAUNCH(16, FUSED);                                             \
+    else if (d <= 4608)                                                     \
+      DG_F16_LAUNCH(8, FUSED);                                              \
+    else                                                                    \
+      DG_F16_LAUNCH(4, FUSED);                                              \
+  } while (0)
+  if (fused)
+    DG_F16_LADDER(true);
+  else
+    DG_F16_LADDER(false);
+#undef DG_F16_LADDER
+#undef DG_F16_LAUNCH
+}
+
+void f32_to_f16_check(hipStream_t s, const float* in, int64_t n, __half* out,
+                      int32_t* overflow) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_f32_to_f16_check, dim3((uint32_t)ceil_div(n, 256)),
+                     dim3(256), 0, s, in, n, out, overflow);
+}
+
+void row_norms_f16(hipStream_t s, const __half* x, int64_t n, int32_t d,
+                   float* out) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_row_norms_f16, dim3((uint32_t)ceil_div(n, 4)),
+                     dim3(256), 0, s, x, n, d, out);
+}
+
+void gather_rows_by_index_f16(hipStream_t s, const __half* src,
+                              const int64_t* idx, int64_t n, int32_t d,
+                              float* dst) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_gather_rows_by_index_f16,
+                     dim3((uint32_t)ceil_div(n * d, 256)), dim3(256), 0, s,
+                     src, idx, n, d, dst);
+}
+
+void transpose_chunks_f16(hipStream_t s, const uint32_t* units,
+                          int32_t n_units, const int64_t* csr_offsets,
+                          const int32_t* chunk_off, const int64_t* chunk_base,
+                          const __half* rowmajor, int32_t d,
+                          int32_t chunk_rows, __half* tvec) {
+  if (!n_units) return;
+  hipLaunchKernelGGL(k_transpose_chunks_f16, dim3((uint32_t)n_units),
+                     dim3(256), 0, s, units, csr_offsets, chunk_off,
+                     chunk_base, rowmajor, d, chunk_rows, tvec);
 }
 
 void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,

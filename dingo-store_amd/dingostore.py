@@ -18,6 +18,15 @@ FLAT, IVF_FLAT, IVF_PQ = 0, 1, 2
 # binary (Hamming) indexes: d is in bits, rows are np.uint8 [n, d // 8]
 BINARY_FLAT, BINARY_IVF_FLAT = 3, 4
 HAMMING = 3
+# row storage of an IVF_FLAT index (dg_storage)
+STORAGE_F32, STORAGE_F16 = 0, 1
+_STORAGE = {"f32": STORAGE_F32, "f16": STORAGE_F16}
+
+
+def _storage_code(storage):
+    if storage not in _STORAGE:
+        raise DgError(f"storage must be 'f32' or 'f16', got {storage!r}")
+    return _STORAGE[storage]
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
@@ -172,6 +181,15 @@ def _load():
     lib.dg_sharded_shard.argtypes = [C.c_void_p, C.c_int32]
     lib.dg_sharded_shard.restype = C.c_void_p
     lib.dg_mirror_selftest_sharded.restype = C.c_int
+    # row storage and read-back
+    lib.dg_set_storage.argtypes = [C.c_void_p, C.c_int32]
+    lib.dg_get_storage.argtypes = [C.c_void_p]
+    lib.dg_get_storage.restype = C.c_int32
+    lib.dg_reconstruct.argtypes = [C.c_void_p, C.c_int64, _i64p, _f32p]
+    lib.dg_last_scan_f16.argtypes = [C.c_void_p]
+    lib.dg_last_scan_f16.restype = C.c_int
+    lib.dg_sharded_set_storage.argtypes = [C.c_void_p, C.c_int32]
+    lib.dg_mirror_selftest_f16.restype = C.c_int
     return lib
 
 
@@ -244,8 +262,12 @@ def make_filter(kind=0, negate=False, min_id=0, max_id=0, ids=None,
 
 class Index:
     def __init__(self, kind, metric, d, nlist=0, m=0, device=-1,
-                 reserve=0, _handle=None, nbits=8):
-        """nbits: IVF-PQ bits per code, 4 or 8 (0 = the default 8)."""
+                 reserve=0, _handle=None, nbits=8, storage="f32"):
+        """nbits: IVF-PQ bits per code, 4 or 8 (0 = the default 8).
+        storage: "f32", or "f16" to keep the rows of an IVF_FLAT index as
+        IEEE halves (dg_set_storage; half the memory and scan bytes, the
+        distances are those to the rounded rows)."""
+        code = _storage_code(storage)
         self.kind, self.metric, self.d = kind, metric, d
         self.nlist = nlist
         self.m = m
@@ -259,6 +281,39 @@ class Index:
         _check(lib().dg_index_create(C.byref(h), C.byref(desc)),
                "dg_index_create")
         self.h = h
+        if code != STORAGE_F32:
+            st = lib().dg_set_storage(self.h, code)
+            if st != 0:
+                msg = last_error()
+                self.close()
+                err = DgError(f"dg_set_storage failed (status {st}): {msg}")
+                err.status = st
+                raise err
+
+    @property
+    def storage(self):
+        """"f32" or "f16" (dg_get_storage)."""
+        return {v: k for k, v in _STORAGE.items()}[
+            lib().dg_get_storage(self.h)]
+
+    def set_storage(self, storage):
+        """Only while the index holds no rows (dg_set_storage)."""
+        _check(lib().dg_set_storage(self.h, _storage_code(storage)),
+               "dg_set_storage")
+
+    def reconstruct(self, ids):
+        """The stored rows of ids decoded to float32 [len(ids), d]; for
+        COSINE the normalised rows.  Every id must be live."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        out = np.empty((len(ids), self.d), np.float32)
+        _check(lib().dg_reconstruct(self.h, len(ids), ids, out),
+               "dg_reconstruct")
+        return out
+
+    def last_scan_f16(self):
+        """True if the last IVF-Flat search that ran its kernels scanned f16
+        rows (dg_last_scan_f16)."""
+        return bool(lib().dg_last_scan_f16(self.h))
 
     def close(self):
         if getattr(self, "h", None):
@@ -666,7 +721,8 @@ class ShardedIndex:
     no save / load, no search batching, no list mask."""
 
     def __init__(self, kind, metric, d, devices, nlist=0, m=0, nbits=8,
-                 reserve=0):
+                 reserve=0, storage="f32"):
+        code = _storage_code(storage)
         self.kind, self.metric, self.d = kind, metric, d
         self.nlist, self.m = nlist, m
         self.nbits = nbits if nbits > 0 else 8
@@ -681,6 +737,15 @@ class ShardedIndex:
             devs if len(devs) else np.zeros(1, np.int32)),
             "dg_sharded_create")
         self.h = h
+        if code != STORAGE_F32:
+            st = lib().dg_sharded_set_storage(self.h, code)
+            if st != 0:
+                msg = last_error()
+                self.close()
+                err = DgError(
+                    f"dg_sharded_set_storage failed (status {st}): {msg}")
+                err.status = st
+                raise err
 
     def close(self):
         if getattr(self, "h", None):

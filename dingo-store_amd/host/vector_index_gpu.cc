@@ -452,6 +452,38 @@ class GpuIvfFlatIndex : public GpuIndexBase {
   int64_t nlist_org_;
 };
 
+// IVF-Flat with the rows stored as IEEE halves (DG_STORAGE_F16).  The
+// reference has no such index: no CPU node could read its snapshot as an
+// IndexIVFFlat, so Save / Load speak the library's own container.
+class GpuIvfFlatF16Index : public GpuIvfFlatIndex {
+ public:
+  GpuIvfFlatF16Index(MetricType m, int32_t d, int32_t nlist, int dev)
+      : GpuIvfFlatIndex(m, d, nlist, dev) {
+    if (create_st_ == DG_OK) create_st_ = dg_set_storage(idx_, DG_STORAGE_F16);
+  }
+  Status Save(const std::string& path) override {
+    return from_dg(dg_save(idx_, path.c_str()));
+  }
+  Status Load(const std::string& path) override {
+    dg_index* ni = nullptr;
+    dg_status st = dg_load(&ni, path.c_str(), -1);
+    if (st != DG_OK) return from_dg(st);
+    dg_stats_out got{};
+    if (dg_stats(ni, &got) != DG_OK || got.kind != DG_INDEX_IVF_FLAT ||
+        got.d != dim_ || got.metric != (int32_t)metric_ ||
+        dg_get_storage(ni) != DG_STORAGE_F16) {
+      dg_index_destroy(ni);
+      return {kEInternal,
+              "loaded index kind, dimension, metric or storage not match"};
+    }
+    dg_index_destroy(idx_);
+    idx_ = ni;
+    if (batching_) return EnableBatching(batch_opts_.max_batch,
+                                         batch_opts_.max_wait_us);
+    return Status::OK();
+  }
+};
+
 class GpuBinaryFlatIndex : public GpuIndexBase {
  public:
   GpuBinaryFlatIndex(int32_t d, int dev)
@@ -836,6 +868,15 @@ std::unique_ptr<VectorIndex> NewFlatIndex(MetricType metric, int32_t dim,
 std::unique_ptr<VectorIndex> NewIvfFlatIndex(MetricType metric, int32_t dim,
                                              int32_t ncentroids, int device) {
   auto p = std::make_unique<GpuIvfFlatIndex>(metric, dim, ncentroids, device);
+  if (!p->CreateStatus().ok()) return nullptr;
+  return p;
+}
+
+std::unique_ptr<VectorIndex> NewIvfFlatIndexF16(MetricType metric, int32_t dim,
+                                                int32_t ncentroids,
+                                                int device) {
+  auto p =
+      std::make_unique<GpuIvfFlatF16Index>(metric, dim, ncentroids, device);
   if (!p->CreateStatus().ok()) return nullptr;
   return p;
 }
@@ -1549,6 +1590,80 @@ bool same_answers(const std::vector<dingogpu::VectorWithDistanceResult>& a,
 }
 
 }  // namespace
+
+extern "C" int dg_mirror_selftest_f16(void) {
+  using namespace dingogpu;
+  if (dg_device_count() == 0) return 1;
+  const int d = 20, nlist = 4, n = 600;
+  std::vector<VectorWithId> batch(n);
+  uint32_t s = 4242;
+  for (int i = 0; i < n; i++) {
+    batch[i].id = i * 3 + 1;
+    batch[i].vector.dimension = d;
+    batch[i].vector.float_values.resize(d);
+    for (int j = 0; j < d; j++) {
+      s = s * 1664525u + 1013904223u;
+      // multiples of 1/64 in [0, 4): exact in half, so a row is its own
+      // stored form and its self distance is exactly 0
+      batch[i].vector.float_values[j] = (float)(s >> 24) / 64.0f;
+    }
+  }
+  VectorSearchParameter p;
+  p.ivf_flat_nprobe = nlist;
+  auto idx = NewIvfFlatIndexF16(MetricType::kL2, d, nlist, -1);
+  if (!idx) return 300;
+  if (idx->IsTrained() || !idx->NeedTrain()) return 301;
+  if (!idx->Train(batch).ok()) return 302;
+  if (!idx->Add(batch).ok()) return 303;
+  int64_t cnt = 0;
+  if (!idx->GetCount(cnt).ok() || cnt != n) return 304;
+  std::vector<VectorWithId> queries(batch.begin(), batch.begin() + 40);
+  std::vector<VectorWithDistanceResult> before, after;
+  if (!idx->Search(queries, 4, {}, false, p, before).ok()) return 305;
+  if (before.size() != queries.size()) return 306;
+  for (size_t i = 0; i < queries.size(); i++) {
+    auto& r = before[i].vector_with_distances;
+    if (r.size() != 4) return 307;
+    if (r[0].distance != 0.0f) return 308;
+    for (size_t j = 1; j < r.size(); j++)
+      if (r[j].distance < r[j - 1].distance) return 309;
+  }
+  // a component no half can hold fails the whole Add
+  std::vector<VectorWithId> bad(batch.begin(), batch.begin() + 2);
+  bad[0].id = 100001;
+  bad[1].id = 100002;
+  bad[1].vector.float_values[3] = 70000.0f;
+  if (idx->Add(bad).code != kEillegalParamteters) return 310;
+  if (!idx->GetCount(cnt).ok() || cnt != n) return 311;
+  // Save (the library's container) -> Load -> the same answers
+  const std::string path = "/tmp/dg_mirror_selftest_f16." +
+                           std::to_string((long)getpid()) + ".dgi";
+  if (!idx->SupportSave() || !idx->Save(path).ok()) return 312;
+  auto fresh = NewIvfFlatIndexF16(MetricType::kL2, d, nlist, -1);
+  Status ls = fresh ? fresh->Load(path) : Status{kEInternal, "create"};
+  remove(path.c_str());
+  if (!ls.ok()) return 313;
+  int64_t cnt2 = 0;
+  if (!fresh->GetCount(cnt2).ok() || cnt2 != n || !fresh->IsTrained())
+    return 314;
+  if (!fresh->Search(queries, 4, {}, false, p, after).ok()) return 315;
+  if (after.size() != before.size()) return 316;
+  for (size_t i = 0; i < before.size(); i++) {
+    auto& a = before[i].vector_with_distances;
+    auto& b = after[i].vector_with_distances;
+    if (a.size() != b.size()) return 317;
+    for (size_t j = 0; j < a.size(); j++) {
+      if (a[j].distance != b[j].distance) return 318;
+      const bool tied =
+          (j && a[j - 1].distance == a[j].distance) ||
+          (j + 1 < a.size() && a[j + 1].distance == a[j].distance) ||
+          j + 1 == a.size();
+      if (!tied && a[j].vector_with_id.id != b[j].vector_with_id.id)
+        return 319;
+    }
+  }
+  return 0;
+}
 
 extern "C" int dg_mirror_selftest_batched(void) {
   using namespace dingogpu;

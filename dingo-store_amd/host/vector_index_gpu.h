@@ -228,6 +228,16 @@ std::unique_ptr<VectorIndex> NewFlatIndex(MetricType metric, int32_t dim,
 std::unique_ptr<VectorIndex> NewIvfFlatIndex(MetricType metric, int32_t dim,
                                              int32_t ncentroids,
                                              int device = -1);
+// IVF-Flat whose rows are stored as IEEE halves (dg_set_storage,
+// DG_STORAGE_F16): half the device memory and half the bytes per search;
+// distances are those between the f32 query and the rounded row.  Add and
+// Upsert fail with EILLEGAL_PARAMTETERS on a component that is NaN or above
+// 65504 in magnitude.  Save and Load use the library's own container
+// (dg_save / dg_load), which no CPU node reads; Load refuses a file of
+// another kind, dimension, metric or storage.
+std::unique_ptr<VectorIndex> NewIvfFlatIndexF16(MetricType metric, int32_t dim,
+                                                int32_t ncentroids,
+                                                int device = -1);
 std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
                                            int32_t ncentroids,
                                            int32_t nsubvector,
@@ -318,6 +328,11 @@ int dg_mirror_selftest_batched(void);
 // order, the 1 - score flip, pads skipped at k above the row count, Delete /
 // Add / Upsert contracts across shards, Save / Load not supported.
 int dg_mirror_selftest_sharded(void);
+// NewIvfFlatIndexF16 through the mirror, on rows that are exact in half:
+// Train -> Add -> self top-1 at distance 0 -> an Add with a component above
+// 65504 refused, the count unchanged -> Save -> Load into a fresh f16 index
+// -> the same top-4, bit for bit.
+int dg_mirror_selftest_f16(void);
 // The second driver of tools/bench_concurrent.py, free of Python threads:
 // `threads` std::threads search the rows of q ([nq x d] float32) round-robin
 // through dg_search (batched = 0) or dg_search_batched, one query per call,

@@ -213,6 +213,43 @@ dg_status dg_upsert(dg_index* idx, int64_t n, const int64_t* ids, const float* x
  * (src/vector/vector_index_ivf_flat.cc:177-186). */
 dg_status dg_remove(dg_index* idx, int64_t n, const int64_t* ids);
 
+/* ---- row storage (opt-in; dg_index_desc is unchanged) ----
+ * DG_STORAGE_F16 keeps the rows of a DG_INDEX_IVF_FLAT index as IEEE halves:
+ * the arrival store and the scanned chunks are half the size and a search
+ * streams half the bytes.  It is accepted only while ntotal == 0 (trained or
+ * not); on a non-empty index or a binary kind the call returns DG_EINVAL, on
+ * FLAT and IVF_PQ DG_ENOT_SUPPORT.  DG_STORAGE_F32 on an empty float index
+ * is always accepted.
+ *   - Centroids, the coarse stage, the assignment and the queries stay f32.
+ *     add / add_device / upsert assign each row from its f32 values (after
+ *     the cosine normalisation), then store it rounded to nearest-even half.
+ *   - A component that is NaN or exceeds 65504 in magnitude fails the whole
+ *     call with DG_EINVAL before anything is appended; dg_upsert makes this
+ *     check before it removes the existing ids, so a refused upsert leaves
+ *     the index as it was.
+ *   - An arrival store reserved at create (desc.reserve) is re-reserved for
+ *     the same number of rows at the new component size.
+ *   - A returned distance is the metric between the f32 query (never rounded
+ *     to half) and the decoded stored row, summed in f32: what faiss QT_fp16
+ *     computes.  For COSINE the stored row is half(f32 normalise(x)); it is
+ *     used as stored and not renormalised, so its norm is 1 +- ~2^-12 and a
+ *     cosine score can exceed 1 by that much.
+ *   - top-k, range search, filters, tombstones, upsert, the list mask, the
+ *     small-batch graph replay, dg_search_batched and dg_export_assign work
+ *     as on an f32 index.  The pair scan is not ported: dg_last_scan_pair
+ *     is 0.  dg_save writes a container of its own (dg_load reads both);
+ *     dg_save_faiss returns DG_ENOT_SUPPORT, no CPU node could read it. */
+typedef enum dg_storage { DG_STORAGE_F32 = 0, DG_STORAGE_F16 = 1 } dg_storage;
+dg_status dg_set_storage(dg_index* idx, int32_t storage);
+int32_t dg_get_storage(dg_index* idx); /* -1 for NULL */
+/* The stored row of each id decoded to f32, out[n x d] at the caller's d
+ * stride (for COSINE the normalised rows).  FLAT and IVF_FLAT, either
+ * storage.  Every id must be live, else DG_ENOT_FOUND and out is untouched;
+ * repeated ids are allowed.  IVF_PQ: DG_ENOT_SUPPORT; binary: DG_EINVAL.
+ * Positions are looked up as dg_remove does (one id download per call). */
+dg_status dg_reconstruct(dg_index* idx, int64_t n, const int64_t* ids,
+                         float* out /* n x d */);
+
 /* ---- search ----
  * Restates VectorIndexIvfFlat::Search (src/vector/vector_index_ivf_flat.cc:
  * 191-275): nprobe <= 0 => index default (80, clamped); nprobe clamped to
@@ -536,6 +573,9 @@ dg_status dg_sharded_range_search(dg_sharded* sh, int64_t nq, const float* x,
 dg_status dg_sharded_stats(dg_sharded* sh, dg_stats_out* out);
 int32_t dg_sharded_n_shards(dg_sharded* sh);
 dg_index* dg_sharded_shard(dg_sharded* sh, int32_t i);
+/* dg_set_storage on every shard, before any row is added (there is no
+ * dg_sharded_reconstruct) */
+dg_status dg_sharded_set_storage(dg_sharded* sh, int32_t storage);
 
 /* ---- wrapper-lifecycle lock (LockWrite/UnlockWrite,
  * vector_index.h:192-193): the exclusive lock the reference wrapper takes
@@ -559,6 +599,9 @@ int dg_last_scan_mfma(dg_index* idx);
  * if k_ivf_scan_mfma took every tile: DG_SCAN_PAIR=0, no more than 16
  * queries, d > 2304, or not the f32-MFMA scan at all. */
 int dg_last_scan_pair(dg_index* idx);
+/* 1 if the last IVF-Flat search that ran its kernels scanned f16 rows
+ * (k_ivf_scan_f16, either candidate flow), 0 otherwise. */
+int dg_last_scan_f16(dg_index* idx);
 int dg_device_count(void);
 /* Library self-identification: returns a static string with build arch. */
 const char* dg_build_info(void);
