@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "dg_internal.h"
+#include "dg_sq8_core.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -483,7 +484,8 @@ extern "C" void dg_index_destroy(dg_index* ix) {
         &ix->d_cb_norms, &ix->ws_T, &ix->ws_Tf32, &ix->ws_queries, &ix->ws_qnorms,
         &ix->ws_dots, &ix->ws_probes, &ix->ws_inv, &ix->ws_cand, &ix->ws_units,
         &ix->ws_small, &ix->ws_topk, &ix->ws_scan, &ix->ws_seg, &ix->ws_gq,
-        &ix->ws_gout, &ix->ws_bm, &ix->ws_partial, &ix->ws_qimage})
+        &ix->ws_gout, &ix->ws_bm, &ix->ws_partial, &ix->ws_qimage,
+        &ix->d_sq, &ix->ws_sq8q})
     dbuf_free(*b);
   if (ix->graph_exec) (void)hipGraphExecDestroy(ix->graph_exec);
   for (auto& e : ix->ev)
@@ -865,6 +867,96 @@ extern "C" dg_status dg_pq_params(dg_index* ix, int32_t* m,
   return DG_OK;
 }
 
+// ---------------- SQ8 ranges ----------------
+// Install validated ranges (d_user values each): host copies for read-back
+// and save, [vmin][vdiff][step] at the padded d on the device (pad dims 0,
+// so a pad component encodes to 0 and decodes to 0).  Caller holds ix->rw.
+static dg_status sq_install_ranges(dg_index* ix, const float* vmin,
+                                   const float* vdiff, const char* fn) {
+  const int32_t d = ix->desc.d, du = ix->d_user;
+  for (int32_t j = 0; j < du; j++)
+    if (!std::isfinite(vmin[j]) || !std::isfinite(vdiff[j]) ||
+        !(vdiff[j] >= 0.0f)) {
+      dg_set_error("%s: range of dimension %d is not finite or vdiff < 0", fn,
+                   j);
+      return DG_EINVAL;
+    }
+  std::vector<float> h((size_t)3 * d, 0.0f);
+  for (int32_t j = 0; j < du; j++) {
+    h[j] = vmin[j];
+    h[d + j] = vdiff[j];
+    h[2 * d + j] = dg_sq8_step(vdiff[j]);
+  }
+  dg_status st = dbuf_reserve(ix->d_sq, (size_t)3 * d * 4, ix->stream, false);
+  if (st != DG_OK) return st;
+  DG_HIP_CHECK(hipMemcpyAsync(ix->d_sq.p, h.data(), (size_t)3 * d * 4,
+                              hipMemcpyHostToDevice, ix->stream));
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  ix->h_sq_vmin.assign(vmin, vmin + du);
+  ix->h_sq_vdiff.assign(vdiff, vdiff + du);
+  ix->sq_has_ranges = true;
+  ix->csr_valid = false;
+  ix->index_gen++;
+  return DG_OK;
+}
+
+// faiss RS_minmax with argument 0 over the (normalised) training rows on the
+// device: vmin = min, vdiff = max - min in f32
+static dg_status sq_train_ranges(dg_index* ix, const float* d_rows,
+                                 int64_t n) {
+  const int32_t d = ix->desc.d;
+  dg_dbuf tmp{};
+  DbufGuard tg(tmp);
+  dg_status st = dbuf_reserve(tmp, (size_t)2 * d * 4, ix->stream, false);
+  if (st != DG_OK) return st;
+  dgk::sq8_col_minmax(ix->stream, d_rows, n, d, (float*)tmp.p,
+                      (float*)tmp.p + d);
+  std::vector<float> h((size_t)2 * d);
+  DG_HIP_CHECK(hipMemcpyAsync(h.data(), tmp.p, (size_t)2 * d * 4,
+                              hipMemcpyDeviceToHost, ix->stream));
+  DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
+  return sq_install_ranges(ix, h.data(), h.data() + d, "dg_train");
+}
+
+extern "C" dg_status dg_set_sq_ranges(dg_index* ix, const float* vmin,
+                                      const float* vdiff) {
+  if (!ix || !vmin || !vdiff) {
+    dg_set_error("bad dg_set_sq_ranges args");
+    return DG_EINVAL;
+  }
+  std::unique_lock lk(ix->rw);
+  if (ix->storage != DG_STORAGE_SQ8) {
+    dg_set_error("dg_set_sq_ranges: the index does not store SQ8 rows");
+    return DG_EINVAL;
+  }
+  if (ix->ntotal != 0) {
+    dg_set_error("dg_set_sq_ranges: the index already holds rows");
+    return DG_EINVAL;
+  }
+  DeviceGuard g(ix->device);
+  return sq_install_ranges(ix, vmin, vdiff, "dg_set_sq_ranges");
+}
+
+extern "C" dg_status dg_get_sq_ranges(dg_index* ix, float* vmin,
+                                      float* vdiff) {
+  if (!ix || !vmin || !vdiff) {
+    dg_set_error("bad dg_get_sq_ranges args");
+    return DG_EINVAL;
+  }
+  std::shared_lock lk(ix->rw);
+  if (ix->storage != DG_STORAGE_SQ8) {
+    dg_set_error("dg_get_sq_ranges: the index does not store SQ8 rows");
+    return DG_EINVAL;
+  }
+  if (!ix->sq_has_ranges) {
+    dg_set_error("dg_get_sq_ranges: no ranges (train or set them)");
+    return DG_ENOT_TRAINED;
+  }
+  memcpy(vmin, ix->h_sq_vmin.data(), (size_t)ix->d_user * 4);
+  memcpy(vdiff, ix->h_sq_vdiff.data(), (size_t)ix->d_user * 4);
+  return DG_OK;
+}
+
 extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
   if (!ix || !x || n <= 0) {
     dg_set_error("bad train args");
@@ -873,11 +965,15 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
   if (!entry_matches(ix, false, "dg_train")) return DG_EINVAL;
   if (ix->desc.kind == DG_INDEX_FLAT) return DG_OK;  // Flat needs no train
   std::unique_lock lk(ix->rw);
-  if (ix->trained) return DG_OK;  // no-op, ivf_flat.cc:669-671
+  // an SQ8 index also needs its ranges; with centroids present only those
+  const bool need_ranges =
+      ix->storage == DG_STORAGE_SQ8 && !ix->sq_has_ranges;
+  const bool need_cents = !ix->trained;
+  if (!need_cents && !need_ranges) return DG_OK;  // no-op, ivf_flat.cc:669-671
   DeviceGuard g(ix->device);
   const int32_t d = ix->desc.d;
   // degrade: data < nlist => nlist = 1 (ivf_flat.cc:676-680)
-  if (n < ix->desc.nlist) ix->desc.nlist = 1;
+  if (need_cents && n < ix->desc.nlist) ix->desc.nlist = 1;
   const int32_t nlist = ix->desc.nlist;
   const uint32_t seed = 1234;  // faiss ClusteringParameters.seed
 
@@ -890,6 +986,10 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
       break;
     if (ix->desc.metric == DG_METRIC_COSINE)
       dgk::normalize_rows(ix->stream, (float*)d_td.p, n, d);
+    if (need_ranges &&
+        (st = sq_train_ranges(ix, (const float*)d_td.p, n)) != DG_OK)
+      break;
+    if (!need_cents) break;
     if ((st = dbuf_reserve(ix->d_centroids, (size_t)nlist * d * 4, ix->stream,
                            false)) != DG_OK ||
         (st = dbuf_reserve(ix->d_cnorms, (size_t)nlist * 4, ix->stream,
@@ -1117,7 +1217,7 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
   const float* x = (const float*)xv;  // float kinds
   std::unique_lock lk(ix->rw);
-  if (!ix->trained) {
+  if (!ix->is_ready()) {
     dg_set_error("IVF index not trained (EVECTOR_NOT_TRAIN)");
     return DG_ENOT_TRAINED;
   }
@@ -1152,6 +1252,7 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   }
   dg_status st = DG_OK;
   const bool is_f16 = ix->storage == DG_STORAGE_F16;
+  const bool is_sq8 = ix->storage == DG_STORAGE_SQ8;
   if (!is_pq && !ix->is_bin)  // PQ never keeps raw vectors (cfg D: 100M x
                               // 768 > HBM); binary keeps packed words
     st = dbuf_reserve(ix->d_vectors, (size_t)(n0 + n) * d * ix->elem_bytes(),
@@ -1191,9 +1292,9 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   }
   dg_dbuf staging{};
   float* dst;
-  if (is_pq || is_f16) {  // stage the incoming chunk (never mutate the
-    // caller's); f16 storage assigns from the f32 staging (+ 4 bytes: the
-    // overflow flag of the conversion) and then stores the halves
+  if (is_pq || is_f16 || is_sq8) {  // stage the incoming chunk (never mutate
+    // the caller's); f16 and SQ8 storage assign from the f32 staging (+ 4
+    // bytes: the flag of the conversion) and then store the halves or codes
     if ((st = dbuf_reserve(staging, (size_t)n * d * 4 + 4, ix->stream,
                            false)) != DG_OK)
       return st;
@@ -1232,6 +1333,15 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
     (void)hipMemcpyAsync(&h_overflow, d_flag, 4, hipMemcpyDeviceToHost,
                          ix->stream);
   }
+  if (is_sq8) {
+    int32_t* d_flag = (int32_t*)((char*)staging.p + (size_t)n * d * 4);
+    const float* sq = (const float*)ix->d_sq.p;
+    (void)hipMemsetAsync(d_flag, 0, 4, ix->stream);
+    dgk::sq8_encode_check(ix->stream, dst, (int64_t)n * d, d, sq, sq + d,
+                          (uint8_t*)ix->d_vectors.p + (size_t)n0 * d, d_flag);
+    (void)hipMemcpyAsync(&h_overflow, d_flag, 4, hipMemcpyDeviceToHost,
+                         ix->stream);
+  }
   {
     const hipError_t e = hipStreamSynchronize(ix->stream);
     if (e != hipSuccess) {
@@ -1240,6 +1350,11 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
     }
   }
   dbuf_free(staging);
+  if (h_overflow && is_sq8) {  // nothing was appended
+    dg_set_error("%s: a component is NaN or infinite; DG_STORAGE_SQ8 cannot "
+                 "store it", fn);
+    return DG_EINVAL;
+  }
   if (h_overflow) {  // nothing was appended: ntotal is unchanged
     dg_set_error("%s: a component is NaN or exceeds the largest finite "
                  "half (65504); DG_STORAGE_F16 cannot store it", fn);
@@ -1407,7 +1522,8 @@ bool dg_contains_id(dg_index* ix, int64_t id) {
 
 // ---------------- row storage ----------------
 extern "C" dg_status dg_set_storage(dg_index* ix, int32_t storage) {
-  if (!ix || (storage != DG_STORAGE_F32 && storage != DG_STORAGE_F16)) {
+  if (!ix || (storage != DG_STORAGE_F32 && storage != DG_STORAGE_F16 &&
+              storage != DG_STORAGE_SQ8)) {
     dg_set_error("bad dg_set_storage args");
     return DG_EINVAL;
   }
@@ -1416,8 +1532,9 @@ extern "C" dg_status dg_set_storage(dg_index* ix, int32_t storage) {
     dg_set_error("dg_set_storage: binary indexes store packed bits");
     return DG_EINVAL;
   }
-  if (storage == DG_STORAGE_F16 && ix->desc.kind != DG_INDEX_IVF_FLAT) {
-    dg_set_error("DG_STORAGE_F16 is implemented for DG_INDEX_IVF_FLAT only");
+  if (storage != DG_STORAGE_F32 && ix->desc.kind != DG_INDEX_IVF_FLAT) {
+    dg_set_error("DG_STORAGE_F16 and DG_STORAGE_SQ8 are implemented for "
+                 "DG_INDEX_IVF_FLAT only");
     return DG_ENOT_SUPPORT;
   }
   if (ix->ntotal != 0) {
@@ -1441,6 +1558,10 @@ extern "C" dg_status dg_set_storage(dg_index* ix, int32_t storage) {
       if (st != DG_OK) return st;
     }
     ix->storage = storage;
+    // leaving SQ8 drops its ranges (entering it starts without any)
+    ix->sq_has_ranges = false;
+    ix->h_sq_vmin.clear();
+    ix->h_sq_vdiff.clear();
     ix->csr_valid = false;
     ix->index_gen++;
   }
@@ -1514,7 +1635,11 @@ extern "C" dg_status dg_reconstruct(dg_index* ix, int64_t n,
   std::lock_guard sg(ix->search_mu);
   DG_HIP_CHECK(hipMemcpyAsync(d_pos, plist.data(), (size_t)n * 8,
                               hipMemcpyHostToDevice, ix->stream));
-  if (ix->storage == DG_STORAGE_F16)
+  if (ix->storage == DG_STORAGE_SQ8)
+    dgk::gather_rows_by_index_sq8(ix->stream, (const uint8_t*)ix->d_vectors.p,
+                                  d_pos, n, d, (const float*)ix->d_sq.p,
+                                  (const float*)ix->d_sq.p + d, d_rows);
+  else if (ix->storage == DG_STORAGE_F16)
     dgk::gather_rows_by_index_f16(ix->stream, (const __half*)ix->d_vectors.p,
                                   d_pos, n, d, d_rows);
   else
@@ -1553,6 +1678,22 @@ static dg_status upsert_impl(dg_index* ix, int64_t n, const int64_t* ids,
           return DG_EINVAL;
         }
       }
+    }
+    // SQ8 storage: NaN and inf are refused (a finite value saturates), and
+    // an index without ranges takes no rows; both before anything is removed
+    if (!binary_entry && ix->storage == DG_STORAGE_SQ8) {
+      if (!ix->is_ready()) {
+        dg_set_error("IVF index not trained (EVECTOR_NOT_TRAIN)");
+        return DG_ENOT_TRAINED;
+      }
+      const float* xf = (const float*)x;
+      const int64_t cnt = n * (int64_t)ix->d_user;
+      for (int64_t i = 0; i < cnt; i++)
+        if (!std::isfinite(xf[i])) {
+          dg_set_error("%s: a component is NaN or infinite; DG_STORAGE_SQ8 "
+                       "cannot store it; nothing was removed", fn);
+          return DG_EINVAL;
+        }
     }
     for (int64_t i = 0; i < n; i++)
       if (ix->id_count.count(ids[i])) existing.push_back(ids[i]);
@@ -1628,7 +1769,8 @@ static dg_status finalize_csr(dg_index* ix) {
     return st;
   // f16 storage (IVF-Flat only): rows, grouped rows and chunks are halves
   const bool is_f16 = is_ivf && ix->storage == DG_STORAGE_F16;
-  const size_t eb = is_f16 ? 2 : 4;
+  const bool is_sq8 = is_ivf && ix->storage == DG_STORAGE_SQ8;
+  const size_t eb = is_f16 ? 2 : is_sq8 ? 1 : 4;
   if (!is_pq &&
       ((st = dbuf_reserve(rowmajor, (size_t)n * d * eb, ix->stream, false)) !=
            DG_OK ||
@@ -1674,6 +1816,13 @@ static dg_status finalize_csr(dg_index* ix) {
       dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_vectors.p, d_perm,
                         n, d * 2, (uint8_t*)rowmajor.p);
       dgk::row_norms_f16(ix->stream, (const __half*)rowmajor.p, n, d,
+                         (float*)ix->d_csr_vnorms.p);
+    } else if (is_sq8) {  // code rows move as d bytes (d % 4 == 0)
+      dgk::gather_codes(ix->stream, (const uint8_t*)ix->d_vectors.p, d_perm,
+                        n, d, (uint8_t*)rowmajor.p);
+      dgk::row_norms_sq8(ix->stream, (const uint8_t*)rowmajor.p, n, d,
+                         (const float*)ix->d_sq.p,
+                         (const float*)ix->d_sq.p + d,
                          (float*)ix->d_csr_vnorms.p);
     } else {
       dgk::gather_rows(ix->stream, (const float*)ix->d_vectors.p, d_perm, n,
@@ -1722,7 +1871,11 @@ static dg_status finalize_csr(dg_index* ix) {
         all_units.push_back((uint32_t)l);
         all_units.push_back((uint32_t)c);
         // f16 chunks pad the dims to 8 (zeros) and count halves
-        t_elems += (int64_t)(is_f16 ? (d + 7) & ~7 : d) * pad;
+        // SQ8 chunks pad the dims to 16 (code 0) and count bytes
+        t_elems += (int64_t)(is_f16   ? (d + 7) & ~7
+                             : is_sq8 ? dg_sq8_dims_pad(d)
+                                      : d) *
+                   pad;
       }
     }
     ix->total_chunks = chunk_off[nlist];
@@ -1751,7 +1904,13 @@ static dg_status finalize_csr(dg_index* ix) {
       dbuf_free(rm_tmp);
       return st;
     }
-    if (is_ivf && !is_f16 &&
+    if (is_sq8 &&  // no slack either (kernels.hip.cpp, SQ8 row storage)
+        (st = dbuf_reserve(ix->d_csr_t, (size_t)t_elems + 64, ix->stream,
+                           false)) != DG_OK) {
+      dbuf_free(rm_tmp);
+      return st;
+    }
+    if (is_ivf && !is_f16 && !is_sq8 &&
         // slack past the last chunk: the glds scan's tail quarters issue
         // padded reads (d columns) and the asm-pipelined scan runs up to 15
         // columns ahead of d (last-iteration issue at base+31); results are
@@ -1782,6 +1941,11 @@ static dg_status finalize_csr(dg_index* ix) {
                                 d_offsets, d_chunk_off, d_chunk_base,
                                 (const __half*)rowmajor.p, d, CR,
                                 (__half*)ix->d_csr_t.p);
+    else if (is_sq8)
+      dgk::transpose_chunks_sq8(ix->stream, d_all_units, ix->total_chunks,
+                                d_offsets, d_chunk_off, d_chunk_base,
+                                (const uint8_t*)rowmajor.p, d, CR,
+                                (uint8_t*)ix->d_csr_t.p);
     else if (is_ivf)
       dgk::transpose_chunks(ix->stream, d_all_units, ix->total_chunks,
                             d_offsets, d_chunk_off, d_chunk_base,
@@ -2283,11 +2447,20 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     // the MFMA body, no pair scan)
     const bool is_f16 = !is_pq && !is_bin && ix->storage == DG_STORAGE_F16;
     ix->last_scan_f16 = is_f16;
-    const bool mfma = fused && (is_f16 || scan_mfma_enabled());
+    const bool is_sq8 = !is_pq && !is_bin && ix->storage == DG_STORAGE_SQ8;
+    ix->last_scan_sq8 = is_sq8;
+    // SQ8: the affine decode is folded into the query once per batch (q'
+    // and cq; kernels.hip.cpp).  The warm run before a graph capture has
+    // reserved this workspace, so the captured launch allocates nothing.
+    if (is_sq8 &&
+        (st = dbuf_reserve(ix->ws_sq8q, (size_t)nq * d * 4 + (size_t)nq * 4,
+                           ix->stream, false)) != DG_OK)
+      return st;
+    const bool mfma = fused && (is_f16 || is_sq8 || scan_mfma_enabled());
     ix->last_scan_mfma = mfma;
     // lists probed by 17+ queries: two query tiles per pass over the rows
     const int32_t pair_py =
-        mfma && !is_f16 && dg_scan_pair_applies((int32_t)d, nq)
+        mfma && !is_f16 && !is_sq8 && dg_scan_pair_applies((int32_t)d, nq)
             ? scan_pair_py()
             : 0;
     ix->last_scan_pair = pair_py > 0;
@@ -2326,6 +2499,7 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     const int64_t row_bytes = is_pq    ? dg_pq_code_size(ix->desc)
                               : is_bin ? (int64_t)(ix->d_user / 8)
                               : is_f16 ? (int64_t)(d * 2 + 4)
+                              : is_sq8 ? (int64_t)(d + 4)
                                        : (int64_t)(d * 4 + 4);
     if (ix->h_pinned && !ix->capturing) {
       dg_dbuf& wsu = ix->ws_units;
@@ -2402,7 +2576,23 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
                           (uint64_t*)(fused ? ix->ws_partial.p
                                             : ix->ws_cand.p),
                           scan_f16_py(mean_probes));
-      else if (fused)
+      else if (is_sq8) {
+        const float* sq = (const float*)ix->d_sq.p;
+        float* qprime = (float*)ix->ws_sq8q.p;
+        float* cq = qprime + (size_t)nq * d;
+        dgk::sq8_fold_query(ix->stream, dq, nq, d, sq, sq + 2 * (size_t)d,
+                            qprime, cq);
+        dgk::ivf_scan_sq8(ix->stream, units, total_units,
+                          (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
+                          d_chunk_base, (const uint8_t*)ix->d_csr_t.p,
+                          (const float*)ix->d_csr_vnorms.p, qprime, cq, d,
+                          inv_offsets32, inv_q, inv_rank, qp_off, q_cand_base,
+                          np, metric, d_bitmap, chunk_rows, fused, k,
+                          ix->cpl_max,
+                          (uint64_t*)(fused ? ix->ws_partial.p
+                                            : ix->ws_cand.p),
+                          scan_f16_py(mean_probes));
+      } else if (fused)
         dgk::ivf_scan_topk(ix->stream, units, total_units,
                            (const int64_t*)ix->d_csr_offsets.p, d_chunk_off,
                            d_chunk_base, (const float*)ix->d_csr_t.p,
@@ -2499,7 +2689,7 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
   }
   DeviceGuard g(ix->device);
   // untrained IVF: blank results, OK (ivf_flat.cc:223-227)
-  if (!ix->trained || ix->ntotal == 0 ||
+  if (!ix->is_ready() || ix->ntotal == 0 ||
       (ix->desc.kind == DG_INDEX_IVF_PQ && !ix->pq_trained)) {
     std::shared_lock lk(ix->rw);
     (void)hipMemsetAsync(d_out_dist, 0, (size_t)nq * k * 4, ix->stream);
@@ -2735,7 +2925,7 @@ extern "C" dg_status dg_range_search(dg_index* ix, int64_t nq, const float* x,
     return DG_ENOT_SUPPORT;
   }
   DeviceGuard g(ix->device);
-  if (!ix->trained || ix->ntotal == 0 ||
+  if (!ix->is_ready() || ix->ntotal == 0 ||
       (ix->desc.kind == DG_INDEX_IVF_PQ && !ix->pq_trained)) {
     memset(lims, 0, ((size_t)nq + 1) * 8);
     *out_ids = (int64_t*)malloc(8);
@@ -2792,7 +2982,7 @@ extern "C" dg_status dg_range_search_binary(dg_index* ix, int64_t nq,
   DeviceGuard g(ix->device);
   // untrained IVF: blank result, OK (ivf_flat.cc:311-315); radius <= 0
   // admits no distance
-  if (!ix->trained || ix->ntotal == 0 || radius <= 0) {
+  if (!ix->is_ready() || ix->ntotal == 0 || radius <= 0) {
     memset(lims, 0, ((size_t)nq + 1) * 8);
     return DG_OK;
   }
@@ -2855,7 +3045,9 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   const int32_t d = ix->desc.d;
   int32_t trained = ix->trained ? 1 : 0;
   const bool is_f16 = ix->storage == DG_STORAGE_F16;
-  if (is_f16) {  // "DGI2": a storage word follows the magic, rows are halves
+  const bool is_sq8 = ix->storage == DG_STORAGE_SQ8;
+  if (is_f16 || is_sq8) {  // "DGI2": a storage word follows the magic, rows
+                           // are halves or SQ8 codes
     fwrite(&kMagicStorage, 4, 1, f);
     fwrite(&ix->storage, 4, 1, f);
   } else {
@@ -2876,6 +3068,14 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
                             ix->desc.nlist) != DG_OK)
       st = DG_EINTERNAL;
     fwrite(cents.data(), 4, cents.size(), f);
+  }
+  if (is_sq8) {  // after the centroids: int32 has_ranges, vmin[d], vdiff[d]
+    const int32_t has = ix->sq_has_ranges ? 1 : 0;
+    fwrite(&has, 4, 1, f);
+    if (has) {
+      fwrite(ix->h_sq_vmin.data(), 4, ix->d_user, f);
+      fwrite(ix->h_sq_vdiff.data(), 4, ix->d_user, f);
+    }
   }
   if (st == DG_OK && is_pq && ix->pq_trained) {
     const int32_t dsub = d / ix->desc.pq_m;
@@ -2900,6 +3100,13 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
                       c * M, hipMemcpyDeviceToHost) != hipSuccess)
           st = DG_EINTERNAL;
         fwrite(cbuf.data(), 1, c * M, f);
+      } else if (is_sq8) {  // d_user codes per row, the pad stripped
+        if (hipMemcpy2D(vbuf.data(), (size_t)ix->d_user,
+                        (const uint8_t*)ix->d_vectors.p + (size_t)s0 * d,
+                        (size_t)d, (size_t)ix->d_user, c,
+                        hipMemcpyDeviceToHost) != hipSuccess)
+          st = DG_EINTERNAL;
+        fwrite(vbuf.data(), 1, c * ix->d_user, f);
       } else if (is_f16) {  // d_user halves per row, the pad stripped
         if (hipMemcpy2D(vbuf.data(), (size_t)ix->d_user * 2,
                         (const __half*)ix->d_vectors.p + (size_t)s0 * d,
@@ -2961,7 +3168,8 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
   if (fread(&magic, 4, 1, f) != 1 ||
       (magic != kMagic && magic != kMagicStorage) ||
       (magic == kMagicStorage &&
-       (fread(&storage, 4, 1, f) != 1 || storage != DG_STORAGE_F16)) ||
+       (fread(&storage, 4, 1, f) != 1 ||
+        (storage != DG_STORAGE_F16 && storage != DG_STORAGE_SQ8))) ||
       fread(&desc, sizeof(desc), 1, f) != 1 || fread(&trained, 4, 1, f) != 1 ||
       fread(&ntotal, 8, 1, f) != 1 || fread(&ndel, 8, 1, f) != 1) {
     fclose(f);
@@ -2979,8 +3187,10 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
   const int32_t d = desc.d;
   const bool is_pq = desc.kind == DG_INDEX_IVF_PQ;
   const bool is_f16 = storage == DG_STORAGE_F16;
+  const bool is_sq8 = storage == DG_STORAGE_SQ8;
   do {
-    if (is_f16 && (st = dg_set_storage(ix, storage)) != DG_OK) break;
+    if ((is_f16 || is_sq8) && (st = dg_set_storage(ix, storage)) != DG_OK)
+      break;
     if (desc.kind != DG_INDEX_FLAT && trained) {
       std::vector<float> cents((size_t)desc.nlist * d);
       if (fread(cents.data(), 4, cents.size(), f) != cents.size()) {
@@ -2989,6 +3199,22 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
       }
       st = dg_set_centroids(ix, desc.nlist, cents.data());
       if (st != DG_OK) break;
+    }
+    if (is_sq8) {
+      int32_t has = 0;
+      if (fread(&has, 4, 1, f) != 1) {
+        st = DG_EIO;
+        break;
+      }
+      if (has) {
+        std::vector<float> r((size_t)2 * d);
+        if (fread(r.data(), 4, r.size(), f) != r.size()) {
+          st = DG_EIO;
+          break;
+        }
+        st = dg_set_sq_ranges(ix, r.data(), r.data() + d);
+        if (st != DG_OK) break;
+      }
     }
     if (is_pq && trained) {
       const int32_t dsub = d / desc.pq_m;
@@ -3012,8 +3238,10 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
                                        (size_t)ntotal * dp * ix->elem_bytes(),
                                        ix->stream, false)) != DG_OK)
         break;
-      if (is_f16 && dp != d)  // the pad columns are never written below
-        (void)hipMemset(ix->d_vectors.p, 0, (size_t)ntotal * dp * 2);
+      if ((is_f16 || is_sq8) && dp != d)  // the pad columns are never
+                                          // written below
+        (void)hipMemset(ix->d_vectors.p, 0,
+                        (size_t)ntotal * dp * ix->elem_bytes());
       if (is_pq && (st = dbuf_reserve(ix->d_codes, (size_t)ntotal * M,
                                       ix->stream, false)) != DG_OK)
         break;
@@ -3032,6 +3260,15 @@ static dg_status dg_load_impl(dg_index** out, const char* path,
           if (hipMemcpy((uint8_t*)ix->d_codes.p + (size_t)s0 * M,
                         cbuf.data(), c * M,
                         hipMemcpyHostToDevice) != hipSuccess)
+            st = DG_EINTERNAL;
+        } else if (is_sq8) {  // stored codes go back bit for bit
+          if (fread(vbuf.data(), 1, c * d, f) != c * d) {
+            st = DG_EIO;
+            break;
+          }
+          if (hipMemcpy2D((uint8_t*)ix->d_vectors.p + (size_t)s0 * dp,
+                          (size_t)dp, vbuf.data(), (size_t)d, (size_t)d, c,
+                          hipMemcpyHostToDevice) != hipSuccess)
             st = DG_EINTERNAL;
         } else if (is_f16) {  // stored halves go back bit for bit
           if (fread(vbuf.data(), 2, c * d, f) != c * d) {
@@ -3109,6 +3346,12 @@ extern "C" int dg_last_scan_pair(dg_index* ix) {
   return ix->last_scan_pair ? 1 : 0;
 }
 
+extern "C" int dg_last_scan_sq8(dg_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard sg(ix->search_mu);
+  return ix->last_scan_sq8 ? 1 : 0;
+}
+
 extern "C" int dg_last_scan_mfma(dg_index* ix) {
   if (!ix) return 0;
   std::lock_guard sg(ix->search_mu);
@@ -3125,13 +3368,13 @@ extern "C" dg_status dg_stats(dg_index* ix, dg_stats_out* out) {
   out->metric = ix->desc.metric;
   out->kind = ix->desc.kind;
   out->nlist = ix->desc.nlist;
-  out->is_trained = ix->trained ? 1 : 0;
+  out->is_trained = ix->is_ready() ? 1 : 0;
   size_t db = 0;
   for (auto b : {&ix->d_vectors, &ix->d_ids, &ix->d_assign, &ix->d_centroids,
                  &ix->d_cnorms, &ix->d_csr_offsets, &ix->d_csr_vectors,
                  &ix->d_csr_ids, &ix->d_csr_vnorms, &ix->d_csr_t,
                  &ix->d_codebooks, &ix->d_codes, &ix->d_csr_codes, &ix->d_S,
-                 &ix->d_cb_norms})
+                 &ix->d_cb_norms, &ix->d_sq})
     db += b->cap;
   out->device_bytes = (int64_t)db;
   out->deleted_count = ix->n_deleted;

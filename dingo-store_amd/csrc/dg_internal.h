@@ -147,7 +147,21 @@ struct dg_index {
   // assignment, queries and d_csr_vnorms (norms of the decoded rows) stay
   // f32.
   int32_t storage = DG_STORAGE_F32;
-  size_t elem_bytes() const { return storage == DG_STORAGE_F16 ? 2 : 4; }
+  size_t elem_bytes() const {
+    return storage == DG_STORAGE_F16 ? 2 : storage == DG_STORAGE_SQ8 ? 1 : 4;
+  }
+  // DG_STORAGE_SQ8: per-dimension ranges of the codec (dg_sq8_core.h).  The
+  // host copies are what dg_get_sq_ranges and dg_save return; d_sq holds
+  // [vmin d][vdiff d][step d] floats at the padded d (pad dims are 0).  An
+  // SQ8 index is trained when it has centroids (trained) and ranges.
+  bool sq_has_ranges = false;
+  std::vector<float> h_sq_vmin, h_sq_vdiff;  // [d_user]
+  dg_dbuf d_sq;
+  dg_dbuf ws_sq8q;  // per batch: q' [nq x d] then cq [nq] (k_sq8_fold_query)
+  bool is_ready() const {
+    return trained && (storage != DG_STORAGE_SQ8 || sq_has_ranges);
+  }
+  bool last_scan_sq8 = false;  // the last search_core scan was k_ivf_scan_sq8
   bool last_scan_f16 = false;  // the last search_core scan was k_ivf_scan_f16
   dg_dbuf d_ids;       // [ntotal] i64
   dg_dbuf d_assign;    // [ntotal] i32 (IVF only; coarse list per vector)
@@ -420,6 +434,44 @@ void ivf_scan_f16(hipStream_t s, const uint32_t* units, int32_t n_units,
                   const uint32_t* bitmap, int32_t chunk_rows, bool fused,
                   int32_t k, int32_t cpl_max, uint64_t* out,
                   int32_t py /* grid.y: a list's tiles are strided over it */);
+// ---- SQ8 row storage (DG_STORAGE_SQ8, IVF-Flat; dg_sq8_core.h) ----
+// out = code of in ([n / d x d] f32 staging); *bad |= 1 on NaN or inf
+void sq8_encode_check(hipStream_t s, const float* in, int64_t n, int32_t d,
+                      const float* vmin, const float* vdiff, uint8_t* out,
+                      int32_t* bad);
+// squared norms of the decoded rows
+void row_norms_sq8(hipStream_t s, const uint8_t* x, int64_t n, int32_t d,
+                   const float* vmin, const float* vdiff, float* out);
+// dst[i] = decoded row idx[i] of src (d bytes per row, d floats out)
+void gather_rows_by_index_sq8(hipStream_t s, const uint8_t* src,
+                              const int64_t* idx, int64_t n, int32_t d,
+                              const float* vmin, const float* vdiff,
+                              float* dst);
+// qp = q * step, cq[i] = sum_j q_ij * (vmin_j + step_j / 2) (f64, rounded
+// once): the affine decode folded into the query, once per batch
+void sq8_fold_query(hipStream_t s, const float* q, int64_t nq, int32_t d,
+                    const float* vmin, const float* step, float* qp,
+                    float* cq);
+// vmin = per-dimension min, vdiff = max - min (f32) of x [n x d]
+void sq8_col_minmax(hipStream_t s, const float* x, int64_t n, int32_t d,
+                    float* vmin, float* vdiff);
+// row-major codes -> the chunk layout of dg_sq8_core.h; chunk_base counts
+// bytes, a chunk is ceil(d/16)*16 x ceil(nrows/4)*4 of them
+void transpose_chunks_sq8(hipStream_t s, const uint32_t* units,
+                          int32_t n_units, const int64_t* csr_offsets,
+                          const int32_t* chunk_off, const int64_t* chunk_base,
+                          const uint8_t* rowmajor, int32_t d,
+                          int32_t chunk_rows, uint8_t* tvec);
+// ivf_scan_f16 over SQ8 chunks; qprime / cq come from sq8_fold_query
+void ivf_scan_sq8(hipStream_t s, const uint32_t* units, int32_t n_units,
+                  const int64_t* csr_offsets, const int32_t* chunk_off,
+                  const int64_t* chunk_base, const uint8_t* tvec,
+                  const float* vnorms, const float* qprime, const float* cq,
+                  int32_t d, const int32_t* inv_offsets, const int32_t* inv_q,
+                  const int32_t* inv_rank, const int64_t* qp_off,
+                  const int64_t* q_cand_base, int32_t nprobe, int metric,
+                  const uint32_t* bitmap, int32_t chunk_rows, bool fused,
+                  int32_t k, int32_t cpl_max, uint64_t* out, int32_t py);
 // range search
 void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,
                 const int64_t* ids_lookup, const float* qnorms, int64_t nq,

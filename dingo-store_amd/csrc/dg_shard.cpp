@@ -175,7 +175,7 @@ dg_status run_on_shards(dg_sharded* sh,
 
 bool is_trained(const dg_sharded* sh) {
   const dg_index* s0 = sh->shards[0];
-  return s0->trained &&
+  return s0->is_ready() &&
          (s0->desc.kind != DG_INDEX_IVF_PQ || s0->pq_trained);
 }
 
@@ -552,6 +552,25 @@ extern "C" dg_status dg_sharded_set_storage(dg_sharded* sh, int32_t storage) {
   return DG_OK;
 }
 
+extern "C" dg_status dg_sharded_set_sq_ranges(dg_sharded* sh,
+                                              const float* vmin,
+                                              const float* vdiff) {
+  if (!sh) return DG_EINVAL;
+  std::unique_lock lk(sh->rw);
+  for (dg_index* ix : sh->shards) {
+    const dg_status st = dg_set_sq_ranges(ix, vmin, vdiff);
+    if (st != DG_OK) return st;
+  }
+  return DG_OK;
+}
+
+extern "C" dg_status dg_sharded_get_sq_ranges(dg_sharded* sh, float* vmin,
+                                              float* vdiff) {
+  if (!sh) return DG_EINVAL;
+  std::shared_lock lk(sh->rw);
+  return dg_get_sq_ranges(sh->shards[0], vmin, vdiff);
+}
+
 // ---------------- train / structure ----------------
 static dg_status replicate_from_shard0(dg_sharded* sh) {
   dg_index* s0 = sh->shards[0];
@@ -565,11 +584,22 @@ static dg_status replicate_from_shard0(dg_sharded* sh) {
     cb.resize((size_t)dg_pq_ksub(s0->desc) * d);  // m * ksub * (d / m)
     if ((st = dg_get_codebooks(s0, cb.data())) != DG_OK) return st;
   }
+  // SQ8: shard 0's ranges go to every shard bit for bit, like the centroids
+  const bool sq8 = dg_get_storage(s0) == DG_STORAGE_SQ8;
+  std::vector<float> rng;
+  if (sq8) {
+    rng.resize((size_t)2 * d);
+    if ((st = dg_get_sq_ranges(s0, rng.data(), rng.data() + d)) != DG_OK)
+      return st;
+  }
   for (int32_t i = 1; i < sh->n; i++) {
     if ((st = dg_set_centroids(sh->shards[i], nlist, cents.data())) != DG_OK)
       return st;
     if (pq && (st = dg_set_codebooks(sh->shards[i], s0->desc.pq_m,
                                      s0->desc.pq_nbits, cb.data())) != DG_OK)
+      return st;
+    if (sq8 && (st = dg_set_sq_ranges(sh->shards[i], rng.data(),
+                                      rng.data() + d)) != DG_OK)
       return st;
   }
   sh->desc.nlist = nlist;

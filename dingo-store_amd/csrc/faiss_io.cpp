@@ -315,7 +315,7 @@ extern "C" dg_status dg_save_faiss(dg_index* ix, const char* path) {
   }
   std::shared_lock lk(ix->rw);
   if (ix->storage != DG_STORAGE_F32) {
-    dg_set_error("dg_save_faiss: f16 row storage would need a scalar-"
+    dg_set_error("dg_save_faiss: f16 or SQ8 row storage would need a scalar-"
                  "quantiser file, which the CPU nodes' IndexIVFFlat loader "
                  "cannot read: use dg_save");
     return DG_ENOT_SUPPORT;

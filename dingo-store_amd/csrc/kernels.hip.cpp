@@ -21,6 +21,7 @@
 
 #include "dg_internal.h"
 #include "dg_shard_core.h"
+#include "dg_sq8_core.h"
 
 #define WAVE 64
 
@@ -2274,6 +2275,337 @@ __global__ void __launch_bounds__(256, 2) k_ivf_scan_f16(
   }
 }
 
+// ---------- SQ8 row storage (DG_STORAGE_SQ8) ----------
+// Rows are stored as one byte per component (dg_sq8_core.h: the codec of
+// faiss QT_8bit with per-dimension ranges); the query stays f32.  The scan
+// does not decode a row: the affine map is folded into the query,
+//   q . x = cq + sum_j (q_j * step_j) * code_j,
+// so k_sq8_fold_query writes q' = q * step and cq once per batch, and
+// k_ivf_scan_sq8 is k_ivf_scan_f16 with q' in its LDS image, the
+// accumulators of a query preset to its cq and the bytes of a loaded dword
+// converted (v_cvt_f32_ubyte0..3) straight into the B operand of the f32
+// MFMA.  Keys, epilogues and everything after the scan see the full dot
+// product.  dg_sq8_core.h documents the chunk layout: one 16-byte load per
+// lane feeds four k-steps (16 dims) for four rows, and every load falls
+// inside its chunk (lanes past nrows_pad re-read its first quad, absent
+// prologue stages re-read its last kp), so the buffer needs no slack.
+__global__ void k_sq8_encode_check(const float* __restrict__ in, int64_t n,
+                                   int32_t d, const float* __restrict__ vmin,
+                                   const float* __restrict__ vdiff,
+                                   uint8_t* __restrict__ out,
+                                   int32_t* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t j = (int32_t)(i % d);
+  const float v = in[i];
+  if (!(fabsf(v) <= 3.402823466e38f)) atomicOr(bad, 1);  // NaN and inf
+  out[i] = dg_sq8_encode(v, vmin[j], vdiff[j]);
+}
+
+__global__ void k_row_norms_sq8(const uint8_t* __restrict__ x, int64_t n,
+                                int32_t d, const float* __restrict__ vmin,
+                                const float* __restrict__ vdiff,
+                                float* __restrict__ out) {
+  const int64_t row = (int64_t)blockIdx.x * (blockDim.x / WAVE) +
+                      threadIdx.x / WAVE;
+  if (row >= n) return;
+  const int lane = threadIdx.x % WAVE;
+  const uint8_t* p = x + (size_t)row * d;
+  float s = 0.f;
+  for (int32_t i = lane; i < d; i += WAVE) {
+    const float v = dg_sq8_decode(p[i], vmin[i], vdiff[i]);
+    s += v * v;
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off);
+  if (lane == 0) out[row] = s;
+}
+
+// out[i] = decoded row idx[i] of src, d bytes per row, d floats out
+__global__ void k_gather_rows_by_index_sq8(const uint8_t* __restrict__ src,
+                                           const int64_t* __restrict__ idx,
+                                           int64_t n, int32_t d,
+                                           const float* __restrict__ vmin,
+                                           const float* __restrict__ vdiff,
+                                           float* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * d) return;
+  const int64_t r = i / d;
+  const int32_t c = (int32_t)(i - r * d);
+  dst[i] = dg_sq8_decode(src[(size_t)idx[r] * d + c], vmin[c], vdiff[c]);
+}
+
+// one block per query: qp = q * step (f32), cq = sum q * (vmin + step / 2)
+// accumulated in f64 and rounded once
+__global__ void __launch_bounds__(256) k_sq8_fold_query(
+    const float* __restrict__ q, int32_t d, const float* __restrict__ vmin,
+    const float* __restrict__ step, float* __restrict__ qp,
+    float* __restrict__ cq) {
+  __shared__ double part[256 / WAVE];
+  const float* src = q + (size_t)blockIdx.x * d;
+  float* dst = qp + (size_t)blockIdx.x * d;
+  double s = 0.0;
+  for (int32_t j = threadIdx.x; j < d; j += blockDim.x) {
+    const float v = src[j], st = step[j];
+    dst[j] = v * st;
+    s += (double)v * ((double)vmin[j] + 0.5 * (double)st);
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off);
+  if (threadIdx.x % WAVE == 0) part[threadIdx.x / WAVE] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < 256 / WAVE; w++) t += part[w];
+    cq[blockIdx.x] = (float)t;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_transpose_chunks_sq8(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const uint8_t* __restrict__ rowmajor, int32_t d, int32_t chunk_rows,
+    uint8_t* __restrict__ tvec) {
+  __shared__ uint8_t tile[64][68];
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t nrows_pad = (nrows + 3) & ~3;
+  const int32_t d16 = dg_sq8_dims_pad(d);
+  const uint8_t* src =
+      rowmajor + (list_start + (int64_t)chunk * chunk_rows) * d;
+  uint8_t* dst = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+
+  const int tx = threadIdx.x % 64;
+  const int ty = threadIdx.x / 64;
+  for (int32_t r0 = 0; r0 < nrows_pad; r0 += 64) {
+    for (int32_t i0 = 0; i0 < d16; i0 += 64) {
+      __syncthreads();
+      for (int rr = ty; rr < 64; rr += 4) {
+        const int32_t r = r0 + rr;
+        tile[rr][tx] = (r < nrows && i0 + tx < d)
+                           ? src[(size_t)r * d + i0 + tx]
+                           : (uint8_t)0;
+      }
+      __syncthreads();
+      // 4 kp x 4 g x 16 quads = 256 16-byte groups per tile, one a thread
+      const int quad = threadIdx.x & 15, g = (threadIdx.x >> 4) & 3,
+                kpl = threadIdx.x >> 6;
+      const int32_t dim0 = i0 + 16 * kpl + g;  // h = 0
+      const int32_t r = r0 + 4 * quad;
+      if (dim0 < d16 && r < nrows_pad) {
+        uint32_t w[4];  // one 16-byte store: chunks are 64-byte aligned
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+          uint32_t v = 0;
+#pragma unroll
+          for (int x = 0; x < 4; x++)
+            v |= (uint32_t)tile[4 * quad + x][16 * kpl + 4 * h + g] << (8 * x);
+          w[h] = v;
+        }
+        *(uint4*)(dst + dg_sq8_chunk_offset(dim0, r, nrows_pad)) =
+            make_uint4(w[0], w[1], w[2], w[3]);
+      }
+    }
+  }
+}
+
+// FUSED: per-wave top-k into `out` (= partial, qp_off / q_cand_base unused);
+// otherwise every candidate into `out` (= cand).  One dot-product body.
+// qprime / cq are what k_sq8_fold_query wrote for this batch.
+template <int QTM, bool FUSED>
+__global__ void __launch_bounds__(256, 2) k_ivf_scan_sq8(
+    const uint32_t* __restrict__ units, const int64_t* __restrict__ csr_offsets,
+    const int32_t* __restrict__ chunk_off, const int64_t* __restrict__ chunk_base,
+    const uint8_t* __restrict__ tvec, const float* __restrict__ vnorms,
+    const float* __restrict__ qprime, const float* __restrict__ cq, int32_t d,
+    const int32_t* __restrict__ inv_offsets, const int32_t* __restrict__ inv_q,
+    const int32_t* __restrict__ inv_rank, const int64_t* __restrict__ qp_off,
+    const int64_t* __restrict__ q_cand_base, int32_t nprobe, int metric,
+    const uint32_t* __restrict__ bitmap, int32_t chunk_rows,
+    uint64_t* __restrict__ out, int32_t kf, int32_t cpl_max) {
+  static_assert(QTM <= 16 && QTM % 4 == 0, "one 16-query MFMA tile");
+  // [nkp][QTM][4][4] floats (one 16-dim period per kp), cbase[QTM], cqs[QTM]
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __builtin_assume(d % 4 == 0 && d > 0);
+  const int32_t nf4 = d >> 2;        // float4s of a query
+  const int32_t nkp = (d + 15) >> 4;  // loads per lane and m: 16 dims each
+  int64_t* cbase = (int64_t*)(smem + (size_t)nkp * QTM * 16);
+  float* cqs = (float*)(cbase + QTM);
+
+  const uint32_t list = units[2 * blockIdx.x];
+  const uint32_t chunk = units[2 * blockIdx.x + 1];
+  const int64_t list_start = csr_offsets[list];
+  const int64_t len = csr_offsets[list + 1] - list_start;
+  const int32_t nrows =
+      (int32_t)min((int64_t)chunk_rows, len - (int64_t)chunk * chunk_rows);
+  const int32_t nrows_pad = (nrows + 3) & ~3;
+  const uint8_t* col = tvec + chunk_base[chunk_off[list] + (int32_t)chunk];
+  const int64_t row0 = list_start + (int64_t)chunk * chunk_rows;
+  const int32_t iq0 = inv_offsets[list];
+  const int32_t nql = inv_offsets[list + 1] - iq0;
+
+  const int wave_id =
+      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  // bytes per kp (16 dims x nrows_pad bytes); a chunk is at most 8192 x 2048
+  // bytes, so 32 bits hold every byte offset into it
+  const uint32_t kstepb = (uint32_t)nrows_pad * 16u;
+
+  // a list's query tiles are strided over grid.y, as in k_ivf_scan_f16
+  for (int32_t t0 = QTM * (int32_t)blockIdx.y; t0 < nql;
+       t0 += QTM * (int32_t)gridDim.y) {
+    const int32_t qt = min(QTM, nql - t0);
+    __syncthreads();
+    // the LDS image of k_ivf_scan_mfma over q': float4 t of query j holds
+    // dims 16kb + 4s + g (kb = t>>2, s = t&3); absent queries and dims are 0
+    const int tid = wave_id * WAVE + dg_lane_id_fresh();
+#pragma unroll 1
+    for (int32_t j = 0; j < QTM; j++) {
+      const float4* src =
+          j < qt ? (const float4*)(qprime +
+                                   (size_t)inv_q[iq0 + t0 + j] * d)
+                 : nullptr;
+      for (int32_t t = tid; t < nkp * 4; t += blockDim.x) {
+        float4 v = float4{0.f, 0.f, 0.f, 0.f};
+        if (src && t < nf4) v = src[t];
+        float* dst = smem + ((size_t)(t >> 2) * QTM + j) * 16 + (t & 3);
+        dst[0] = v.x;
+        dst[4] = v.y;
+        dst[8] = v.z;
+        dst[12] = v.w;
+      }
+    }
+    if (tid < QTM) {
+      const int32_t j = tid;
+      int64_t cb = 0;
+      float c0 = 0.f;
+      if (j < qt) {
+        const int32_t q = inv_q[iq0 + t0 + j];
+        const int32_t rank = inv_rank[iq0 + t0 + j];
+        c0 = cq[q];
+        if (FUSED)
+          cb = ((((int64_t)q * nprobe + rank) * cpl_max + chunk) *
+                (chunk_rows / (WAVE * 4))) * kf;
+        else
+          cb = q_cand_base[q] + qp_off[(int64_t)q * nprobe + rank] +
+               (int64_t)chunk * chunk_rows;
+      }
+      cbase[j] = cb;
+      cqs[j] = c0;
+    }
+    __syncthreads();
+
+    for (int32_t rb = wave_id * WAVE * 4; rb < nrows_pad; rb += 4 * WAVE * 4) {
+      const int lane = dg_lane_id_fresh();
+      const int g = lane >> 4, i = lane & 15;
+      uint32_t voff[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const int32_t rr = rb + 64 * m + 4 * i;
+        voff[m] = ((uint32_t)g * (uint32_t)nrows_pad +
+                   (uint32_t)(rr < nrows_pad ? rr : 0)) * 4u;
+      }
+      const dg_acc4* ap = (const dg_acc4*)smem + (i < QTM ? i : 0) * 4 + g;
+
+      // the accumulators of query 4g + rq start at its cq (0 past QTM)
+      dg_acc4 c4 = dg_acc4{0.f, 0.f, 0.f, 0.f};
+      if (4 * g < QTM) c4 = *(const dg_acc4*)(cqs + 4 * g);
+      dg_acc4 acc[4][4];
+#pragma unroll
+      for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int x = 0; x < 4; x++) acc[m][x] = c4;
+      uint4 b0[4], b1[4], b2[4], b3[4];
+      auto issue = [&](uint4 (&b)[4], int32_t kp) {
+        const uint32_t uo =
+            __builtin_amdgcn_readfirstlane((uint32_t)kp * kstepb);
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+          b[m] = *(const uint4*)(col + (voff[m] + uo));
+      };
+      // k-steps 4kp + h (a[h]: dims 16kp + 4h + g), h = 0..3 in order
+      auto compute = [&](const uint4 (&b)[4], const dg_acc4 a) {
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+#pragma unroll
+          for (int m = 0; m < 4; m++) {
+            const uint32_t w = h == 0   ? b[m].x
+                               : h == 1 ? b[m].y
+                               : h == 2 ? b[m].z
+                                        : b[m].w;
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+              acc[m][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                  a[h], (float)((w >> (8 * x)) & 0xffu), acc[m][x], 0, 0, 0);
+          }
+        }
+      };
+      auto qload = [&]() {
+        dg_acc4 a = *ap;
+        ap += QTM * 4;
+        if (QTM < 16 && i >= QTM) a = dg_acc4{0.f, 0.f, 0.f, 0.f};
+        return a;
+      };
+
+      // modulo schedule as in k_ivf_scan_f16; a stage is one kp (16 dims
+      // and one LDS read), a period four stages = 64 dims
+      issue(b0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b1, min(1, nkp - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b2, min(2, nkp - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      issue(b3, min(3, nkp - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      int32_t kp = 0;
+      for (; kp + 8 <= nkp; kp += 4) {  // the next period is whole too
+        compute(b0, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b0, kp + 4);
+        compute(b1, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b1, kp + 5);
+        compute(b2, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b2, kp + 6);
+        compute(b3, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b3, kp + 7);
+      }
+      if (kp + 4 < nkp) {  // whole period followed by a 1..3-stage one
+        const int32_t rem = nkp - kp - 4;
+        compute(b0, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        issue(b0, kp + 4);
+        compute(b1, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        if (rem > 1) issue(b1, kp + 5);
+        compute(b2, qload());
+        __builtin_amdgcn_sched_barrier(0);
+        if (rem > 2) issue(b2, kp + 6);
+        compute(b3, qload());
+        kp += 4;
+      }
+      {  // last period: 1..4 stages; absent stages are skipped
+        const int32_t rem = nkp - kp;
+        compute(b0, qload());
+        if (rem > 1) compute(b1, qload());
+        if (rem > 2) compute(b2, qload());
+        if (rem > 3) compute(b3, qload());
+      }
+      if (FUSED)
+        dg_scan_topk_epilogue_mfma(acc, cbase,
+                                   (int64_t)(rb / (WAVE * 4)) * kf, vnorms,
+                                   nrows, rb, row0, qt, metric, bitmap, kf,
+                                   out);
+      else
+        dg_scan_store_epilogue_mfma(acc, cbase, vnorms, nrows, rb, row0, qt,
+                                    metric, bitmap, out);
+    }
+  }
+}
+
 // ---------- pair scan: two query tiles per pass over a chunk's rows ------
 // A list probed by more than 16 queries costs k_ivf_scan_mfma one HBM pass
 // over its chunk per 16-query tile.  k_ivf_scan_mfma2 feeds each k-step's
@@ -4095,6 +4427,124 @@ void transpose_chunks_f16(hipStream_t s, const uint32_t* units,
   hipLaunchKernelGGL(k_transpose_chunks_f16, dim3((uint32_t)n_units),
                      dim3(256), 0, s, units, csr_offsets, chunk_off,
                      chunk_base, rowmajor, d, chunk_rows, tvec);
+}
+
+void ivf_scan_sq8(hipStream_t s, const uint32_t* units, int32_t n_units,
+                  const int64_t* csr_offsets, const int32_t* chunk_off,
+                  const int64_t* chunk_base, const uint8_t* tvec,
+                  const float* vnorms, const float* qprime, const float* cq,
+                  int32_t d, const int32_t* inv_offsets, const int32_t* inv_q,
+                  const int32_t* inv_rank, const int64_t* qp_off,
+                  const int64_t* q_cand_base, int32_t nprobe, int metric,
+                  const uint32_t* bitmap, int32_t chunk_rows, bool fused,
+                  int32_t k, int32_t cpl_max, uint64_t* out, int32_t py) {
+  if (!n_units) return;
+  // the tile ladder of k_ivf_scan_mfma; the LDS image is one 16-dim period
+  // per kp, then cbase and the tile's cq
+#define DG_SQ8_LAUNCH(QTM, FUSED)                                           \
+  do {                                                                      \
+    size_t lds = (size_t)((d + 15) / 16) * (QTM) * 64 + (QTM) * 12;         \
+    hipLaunchKernelGGL((k_ivf_scan_sq8<(QTM), (FUSED)>),                    \
+                       dim3((uint32_t)n_units, (uint32_t)py), dim3(256),    \
+                       lds, s, units, csr_offsets, chunk_off, chunk_base,   \
+                       tvec, vnorms, qprime, cq, d, inv_offsets, inv_q,     \
+                       inv_rank, qp_off, q_cand_base, nprobe, metric,       \
+                       bitmap, chunk_rows, out, k, cpl_max);                \
+  } while (0)
+#define DG_SQ8_LADDER(FUSED)                                                \
+  do {                                                                      \
+    if (d <= 2304)                                                          \
+      DG_SQ8_LAUNCH(16, FUSED);                                             \
+    else if (d <= 4608)                                                     \
+      DG_SQ8_LAUNCH(8, FUSED);                                              \
+    else                                                                    \
+      DG_SQ8_LAUNCH(4, FUSED);                                              \
+  } while (0)
+  if (fused)
+    DG_SQ8_LADDER(true);
+  else
+    DG_SQ8_LADDER(false);
+#undef DG_SQ8_LADDER
+#undef DG_SQ8_LAUNCH
+}
+
+void sq8_encode_check(hipStream_t s, const float* in, int64_t n, int32_t d,
+                      const float* vmin, const float* vdiff, uint8_t* out,
+                      int32_t* bad) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_sq8_encode_check, dim3((uint32_t)ceil_div(n, 256)),
+                     dim3(256), 0, s, in, n, d, vmin, vdiff, out, bad);
+}
+
+void row_norms_sq8(hipStream_t s, const uint8_t* x, int64_t n, int32_t d,
+                   const float* vmin, const float* vdiff, float* out) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_row_norms_sq8, dim3((uint32_t)ceil_div(n, 4)),
+                     dim3(256), 0, s, x, n, d, vmin, vdiff, out);
+}
+
+void gather_rows_by_index_sq8(hipStream_t s, const uint8_t* src,
+                              const int64_t* idx, int64_t n, int32_t d,
+                              const float* vmin, const float* vdiff,
+                              float* dst) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_gather_rows_by_index_sq8,
+                     dim3((uint32_t)ceil_div(n * d, 256)), dim3(256), 0, s,
+                     src, idx, n, d, vmin, vdiff, dst);
+}
+
+void sq8_fold_query(hipStream_t s, const float* q, int64_t nq, int32_t d,
+                    const float* vmin, const float* step, float* qp,
+                    float* cq) {
+  if (nq <= 0) return;
+  hipLaunchKernelGGL(k_sq8_fold_query, dim3((uint32_t)nq), dim3(256), 0, s,
+                     q, d, vmin, step, qp, cq);
+}
+
+void transpose_chunks_sq8(hipStream_t s, const uint32_t* units,
+                          int32_t n_units, const int64_t* csr_offsets,
+                          const int32_t* chunk_off, const int64_t* chunk_base,
+                          const uint8_t* rowmajor, int32_t d,
+                          int32_t chunk_rows, uint8_t* tvec) {
+  if (!n_units) return;
+  hipLaunchKernelGGL(k_transpose_chunks_sq8, dim3((uint32_t)n_units),
+                     dim3(256), 0, s, units, csr_offsets, chunk_off,
+                     chunk_base, rowmajor, d, chunk_rows, tvec);
+}
+
+// per-dimension min and max - min (f32) of x [n x d], for dg_train
+__global__ void __launch_bounds__(256) k_sq8_col_minmax(
+    const float* __restrict__ x, int64_t n, int32_t d,
+    float* __restrict__ vmin, float* __restrict__ vdiff) {
+  __shared__ float smin[256], smax[256];
+  const int32_t j = blockIdx.x;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
+    const float v = x[(size_t)r * d + j];
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+  smin[threadIdx.x] = lo;
+  smax[threadIdx.x] = hi;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+      smin[threadIdx.x] = fminf(smin[threadIdx.x], smin[threadIdx.x + off]);
+      smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + off]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    vmin[j] = smin[0];
+    vdiff[j] = smax[0] - smin[0];
+  }
+}
+
+void sq8_col_minmax(hipStream_t s, const float* x, int64_t n, int32_t d,
+                    float* vmin, float* vdiff) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_sq8_col_minmax, dim3((uint32_t)d), dim3(256), 0, s, x,
+                     n, d, vmin, vdiff);
 }
 
 void range_emit(hipStream_t s, const uint64_t* packed, const int64_t* lims,

@@ -19,13 +19,14 @@ FLAT, IVF_FLAT, IVF_PQ = 0, 1, 2
 BINARY_FLAT, BINARY_IVF_FLAT = 3, 4
 HAMMING = 3
 # row storage of an IVF_FLAT index (dg_storage)
-STORAGE_F32, STORAGE_F16 = 0, 1
-_STORAGE = {"f32": STORAGE_F32, "f16": STORAGE_F16}
+STORAGE_F32, STORAGE_F16, STORAGE_SQ8 = 0, 1, 2
+_STORAGE = {"f32": STORAGE_F32, "f16": STORAGE_F16, "sq8": STORAGE_SQ8}
 
 
 def _storage_code(storage):
     if storage not in _STORAGE:
-        raise DgError(f"storage must be 'f32' or 'f16', got {storage!r}")
+        raise DgError(
+            f"storage must be 'f32', 'f16' or 'sq8', got {storage!r}")
     return _STORAGE[storage]
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -190,6 +191,14 @@ def _load():
     lib.dg_last_scan_f16.restype = C.c_int
     lib.dg_sharded_set_storage.argtypes = [C.c_void_p, C.c_int32]
     lib.dg_mirror_selftest_f16.restype = C.c_int
+    # SQ8 row storage
+    lib.dg_set_sq_ranges.argtypes = [C.c_void_p, _f32p, _f32p]
+    lib.dg_get_sq_ranges.argtypes = [C.c_void_p, _f32p, _f32p]
+    lib.dg_last_scan_sq8.argtypes = [C.c_void_p]
+    lib.dg_last_scan_sq8.restype = C.c_int
+    lib.dg_sharded_set_sq_ranges.argtypes = [C.c_void_p, _f32p, _f32p]
+    lib.dg_sharded_get_sq_ranges.argtypes = [C.c_void_p, _f32p, _f32p]
+    lib.dg_mirror_selftest_sq8.restype = C.c_int
     return lib
 
 
@@ -266,7 +275,10 @@ class Index:
         """nbits: IVF-PQ bits per code, 4 or 8 (0 = the default 8).
         storage: "f32", or "f16" to keep the rows of an IVF_FLAT index as
         IEEE halves (dg_set_storage; half the memory and scan bytes, the
-        distances are those to the rounded rows)."""
+        distances are those to the rounded rows), or "sq8" for one byte per
+        component (per-dimension 8-bit scalar quantisation; a quarter of the
+        memory and scan bytes; train() or set_sq_ranges() gives the ranges,
+        the distances are those to the decoded rows)."""
         code = _storage_code(storage)
         self.kind, self.metric, self.d = kind, metric, d
         self.nlist = nlist
@@ -292,7 +304,7 @@ class Index:
 
     @property
     def storage(self):
-        """"f32" or "f16" (dg_get_storage)."""
+        """"f32", "f16" or "sq8" (dg_get_storage)."""
         return {v: k for k, v in _STORAGE.items()}[
             lib().dg_get_storage(self.h)]
 
@@ -309,6 +321,28 @@ class Index:
         _check(lib().dg_reconstruct(self.h, len(ids), ids, out),
                "dg_reconstruct")
         return out
+
+    def set_sq_ranges(self, vmin, vdiff):
+        """Per-dimension ranges of an empty SQ8 index (dg_set_sq_ranges)."""
+        vmin = np.ascontiguousarray(vmin, np.float32).reshape(-1)
+        vdiff = np.ascontiguousarray(vdiff, np.float32).reshape(-1)
+        if len(vmin) != self.d or len(vdiff) != self.d:
+            raise DgError(f"ranges must hold d = {self.d} values each")
+        _check(lib().dg_set_sq_ranges(self.h, vmin, vdiff),
+               "dg_set_sq_ranges")
+
+    def get_sq_ranges(self):
+        """(vmin, vdiff), float32 [d] each (dg_get_sq_ranges)."""
+        vmin = np.empty(self.d, np.float32)
+        vdiff = np.empty(self.d, np.float32)
+        _check(lib().dg_get_sq_ranges(self.h, vmin, vdiff),
+               "dg_get_sq_ranges")
+        return vmin, vdiff
+
+    def last_scan_sq8(self):
+        """True if the last IVF-Flat search that ran its kernels scanned SQ8
+        rows (dg_last_scan_sq8)."""
+        return bool(lib().dg_last_scan_sq8(self.h))
 
     def last_scan_f16(self):
         """True if the last IVF-Flat search that ran its kernels scanned f16
@@ -776,6 +810,23 @@ class ShardedIndex:
         _check(lib().dg_sharded_get_centroids(self.h, out),
                "dg_sharded_get_centroids")
         return out
+
+    def set_sq_ranges(self, vmin, vdiff):
+        """The SQ8 ranges of every (empty) shard."""
+        vmin = np.ascontiguousarray(vmin, np.float32).reshape(-1)
+        vdiff = np.ascontiguousarray(vdiff, np.float32).reshape(-1)
+        if len(vmin) != self.d or len(vdiff) != self.d:
+            raise DgError(f"ranges must hold d = {self.d} values each")
+        _check(lib().dg_sharded_set_sq_ranges(self.h, vmin, vdiff),
+               "dg_sharded_set_sq_ranges")
+
+    def get_sq_ranges(self):
+        """(vmin, vdiff) of shard 0; every shard holds the same."""
+        vmin = np.empty(self.d, np.float32)
+        vdiff = np.empty(self.d, np.float32)
+        _check(lib().dg_sharded_get_sq_ranges(self.h, vmin, vdiff),
+               "dg_sharded_get_sq_ranges")
+        return vmin, vdiff
 
     def set_codebooks(self, codebooks):
         """codebooks: [m, 2**nbits, d//m] float32."""

@@ -457,9 +457,10 @@ class GpuIvfFlatIndex : public GpuIndexBase {
 // IndexIVFFlat, so Save / Load speak the library's own container.
 class GpuIvfFlatF16Index : public GpuIvfFlatIndex {
  public:
-  GpuIvfFlatF16Index(MetricType m, int32_t d, int32_t nlist, int dev)
-      : GpuIvfFlatIndex(m, d, nlist, dev) {
-    if (create_st_ == DG_OK) create_st_ = dg_set_storage(idx_, DG_STORAGE_F16);
+  GpuIvfFlatF16Index(MetricType m, int32_t d, int32_t nlist, int dev,
+                     int32_t storage = DG_STORAGE_F16)
+      : GpuIvfFlatIndex(m, d, nlist, dev), storage_(storage) {
+    if (create_st_ == DG_OK) create_st_ = dg_set_storage(idx_, storage_);
   }
   Status Save(const std::string& path) override {
     return from_dg(dg_save(idx_, path.c_str()));
@@ -471,7 +472,7 @@ class GpuIvfFlatF16Index : public GpuIvfFlatIndex {
     dg_stats_out got{};
     if (dg_stats(ni, &got) != DG_OK || got.kind != DG_INDEX_IVF_FLAT ||
         got.d != dim_ || got.metric != (int32_t)metric_ ||
-        dg_get_storage(ni) != DG_STORAGE_F16) {
+        dg_get_storage(ni) != storage_) {
       dg_index_destroy(ni);
       return {kEInternal,
               "loaded index kind, dimension, metric or storage not match"};
@@ -482,6 +483,18 @@ class GpuIvfFlatF16Index : public GpuIvfFlatIndex {
                                          batch_opts_.max_wait_us);
     return Status::OK();
   }
+
+ protected:
+  int32_t storage_;
+};
+
+// IVF-Flat with one byte per component (DG_STORAGE_SQ8).  Train yields the
+// per-dimension ranges next to the centroids (dg_train); Save / Load speak
+// the library's own container, as for f16.
+class GpuIvfFlatSq8Index : public GpuIvfFlatF16Index {
+ public:
+  GpuIvfFlatSq8Index(MetricType m, int32_t d, int32_t nlist, int dev)
+      : GpuIvfFlatF16Index(m, d, nlist, dev, DG_STORAGE_SQ8) {}
 };
 
 class GpuBinaryFlatIndex : public GpuIndexBase {
@@ -877,6 +890,15 @@ std::unique_ptr<VectorIndex> NewIvfFlatIndexF16(MetricType metric, int32_t dim,
                                                 int device) {
   auto p =
       std::make_unique<GpuIvfFlatF16Index>(metric, dim, ncentroids, device);
+  if (!p->CreateStatus().ok()) return nullptr;
+  return p;
+}
+
+std::unique_ptr<VectorIndex> NewIvfFlatIndexSq8(MetricType metric, int32_t dim,
+                                                int32_t ncentroids,
+                                                int device) {
+  auto p =
+      std::make_unique<GpuIvfFlatSq8Index>(metric, dim, ncentroids, device);
   if (!p->CreateStatus().ok()) return nullptr;
   return p;
 }
@@ -1660,6 +1682,90 @@ extern "C" int dg_mirror_selftest_f16(void) {
           j + 1 == a.size();
       if (!tied && a[j].vector_with_id.id != b[j].vector_with_id.id)
         return 319;
+    }
+  }
+  return 0;
+}
+
+extern "C" int dg_mirror_selftest_sq8(void) {
+  using namespace dingogpu;
+  if (dg_device_count() == 0) return 1;
+  const int d = 20, nlist = 4, n = 600;
+  std::vector<VectorWithId> batch(n);
+  uint32_t s = 777;
+  for (int i = 0; i < n; i++) {
+    batch[i].id = i * 3 + 1;
+    batch[i].vector.dimension = d;
+    batch[i].vector.float_values.resize(d);
+    for (int j = 0; j < d; j++) {
+      s = s * 1664525u + 1013904223u;
+      batch[i].vector.float_values[j] = (float)(s >> 20) / 1024.0f;  // [0, 4)
+    }
+  }
+  VectorSearchParameter p;
+  p.ivf_flat_nprobe = nlist;
+  auto idx = NewIvfFlatIndexSq8(MetricType::kL2, d, nlist, -1);
+  if (!idx) return 400;
+  if (idx->IsTrained() || !idx->NeedTrain()) return 401;
+  // no ranges yet: Add is refused
+  if (idx->Add(batch).ok()) return 402;
+  if (!idx->Train(batch).ok()) return 403;  // centroids and ranges
+  if (!idx->IsTrained()) return 404;
+  if (!idx->Add(batch).ok()) return 405;
+  int64_t cnt = 0;
+  if (!idx->GetCount(cnt).ok() || cnt != n) return 406;
+  std::vector<VectorWithId> queries(batch.begin(), batch.begin() + 40);
+  std::vector<VectorWithDistanceResult> before, after;
+  if (!idx->Search(queries, 4, {}, false, p, before).ok()) return 407;
+  if (before.size() != queries.size()) return 408;
+  // a row lies within half a step (range / 510, range < 4) of its stored
+  // form in every dimension: its self distance is below d * (4 / 510)^2,
+  // three orders of magnitude under the distance to another row
+  const float self_max = d * (4.0f / 510.0f) * (4.0f / 510.0f) * 1.01f;
+  for (size_t i = 0; i < queries.size(); i++) {
+    auto& r = before[i].vector_with_distances;
+    if (r.size() != 4) return 409;
+    if (r[0].vector_with_id.id != queries[i].id) return 410;
+    if (!(r[0].distance <= self_max)) return 411;
+    for (size_t j = 1; j < r.size(); j++)
+      if (r[j].distance < r[j - 1].distance) return 412;
+  }
+  // a NaN component fails the whole Add
+  std::vector<VectorWithId> bad(batch.begin(), batch.begin() + 2);
+  bad[0].id = 100001;
+  bad[1].id = 100002;
+  bad[1].vector.float_values[3] = std::nanf("");
+  if (idx->Add(bad).code != kEillegalParamteters) return 413;
+  if (!idx->GetCount(cnt).ok() || cnt != n) return 414;
+  // Save (the library's container) -> Load -> the same answers
+  const std::string path = "/tmp/dg_mirror_selftest_sq8." +
+                           std::to_string((long)getpid()) + ".dgi";
+  if (!idx->SupportSave() || !idx->Save(path).ok()) return 415;
+  auto fresh = NewIvfFlatIndexSq8(MetricType::kL2, d, nlist, -1);
+  Status ls = fresh ? fresh->Load(path) : Status{kEInternal, "create"};
+  // an f16 index refuses the SQ8 file
+  auto other = NewIvfFlatIndexF16(MetricType::kL2, d, nlist, -1);
+  const bool refused = other && !other->Load(path).ok();
+  remove(path.c_str());
+  if (!ls.ok()) return 416;
+  if (!refused) return 417;
+  int64_t cnt2 = 0;
+  if (!fresh->GetCount(cnt2).ok() || cnt2 != n || !fresh->IsTrained())
+    return 418;
+  if (!fresh->Search(queries, 4, {}, false, p, after).ok()) return 419;
+  if (after.size() != before.size()) return 420;
+  for (size_t i = 0; i < before.size(); i++) {
+    auto& a = before[i].vector_with_distances;
+    auto& b = after[i].vector_with_distances;
+    if (a.size() != b.size()) return 421;
+    for (size_t j = 0; j < a.size(); j++) {
+      if (a[j].distance != b[j].distance) return 422;
+      const bool tied =
+          (j && a[j - 1].distance == a[j].distance) ||
+          (j + 1 < a.size() && a[j + 1].distance == a[j].distance) ||
+          j + 1 == a.size();
+      if (!tied && a[j].vector_with_id.id != b[j].vector_with_id.id)
+        return 423;
     }
   }
   return 0;

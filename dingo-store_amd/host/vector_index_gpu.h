@@ -238,6 +238,17 @@ std::unique_ptr<VectorIndex> NewIvfFlatIndex(MetricType metric, int32_t dim,
 std::unique_ptr<VectorIndex> NewIvfFlatIndexF16(MetricType metric, int32_t dim,
                                                 int32_t ncentroids,
                                                 int device = -1);
+// IVF-Flat whose rows are stored as one byte per component (dg_set_storage,
+// DG_STORAGE_SQ8: the codec of faiss QT_8bit): a quarter of the device
+// memory and of the bytes per search; distances are those between the f32
+// query and the decoded row.  Train yields the per-dimension ranges (min and
+// max - min of the training rows) next to the centroids, and IsTrained needs
+// both.  A component outside its range saturates; Add and Upsert fail with
+// EILLEGAL_PARAMTETERS on a NaN or infinite component.  Save and Load as for
+// NewIvfFlatIndexF16.
+std::unique_ptr<VectorIndex> NewIvfFlatIndexSq8(MetricType metric, int32_t dim,
+                                                int32_t ncentroids,
+                                                int device = -1);
 std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
                                            int32_t ncentroids,
                                            int32_t nsubvector,
@@ -333,6 +344,12 @@ int dg_mirror_selftest_sharded(void);
 // 65504 refused, the count unchanged -> Save -> Load into a fresh f16 index
 // -> the same top-4, bit for bit.
 int dg_mirror_selftest_f16(void);
+// NewIvfFlatIndexSq8 through the mirror: an Add before Train refused ->
+// Train (centroids and ranges) -> Add -> self top-1 within half a step per
+// dimension -> an Add with a NaN component refused, the count unchanged ->
+// Save -> Load into a fresh SQ8 index (an f16 index refuses the file) -> the
+// same top-4, bit for bit.
+int dg_mirror_selftest_sq8(void);
 // The second driver of tools/bench_concurrent.py, free of Python threads:
 // `threads` std::threads search the rows of q ([nq x d] float32) round-robin
 // through dg_search (batched = 0) or dg_search_batched, one query per call,

@@ -238,10 +238,47 @@ dg_status dg_remove(dg_index* idx, int64_t n, const int64_t* ids);
  *     small-batch graph replay, dg_search_batched and dg_export_assign work
  *     as on an f32 index.  The pair scan is not ported: dg_last_scan_pair
  *     is 0.  dg_save writes a container of its own (dg_load reads both);
- *     dg_save_faiss returns DG_ENOT_SUPPORT, no CPU node could read it. */
-typedef enum dg_storage { DG_STORAGE_F32 = 0, DG_STORAGE_F16 = 1 } dg_storage;
+ *     dg_save_faiss returns DG_ENOT_SUPPORT, no CPU node could read it.
+ *
+ * DG_STORAGE_SQ8 keeps one byte per component: per-dimension 8-bit scalar
+ * quantisation, the codec of faiss QT_8bit, in f32 with ranges (vmin, vdiff):
+ *     encode  t = vdiff_j > 0 ? (x - vmin_j) / vdiff_j : 0, clamped to [0, 1],
+ *             code = (uint8)(int)(255.0f * t)
+ *     decode  vmin_j + ((code + 0.5f) / 255.0f) * vdiff_j
+ * It is accepted, refused and left under exactly the rules of F16; leaving
+ * SQ8 drops its ranges.  What differs from F16:
+ *   - The index is trained when it has centroids AND ranges: dg_stats
+ *     .is_trained, the blank search on an untrained index and DG_ENOT_TRAINED
+ *     from add / upsert follow that.  dg_train on an SQ8 index without ranges
+ *     computes them from all n training rows after the cosine normalisation:
+ *     per-dimension min, and vdiff = max - min in f32 (faiss RS_minmax with
+ *     argument 0); if centroids are already present it trains the ranges
+ *     only.  dg_set_sq_ranges injects ranges instead.
+ *   - A component outside its range saturates, as in faiss.  A NaN or
+ *     infinite component fails the whole add / upsert with DG_EINVAL before
+ *     anything moves (upsert checks before it removes).
+ *   - A returned distance is the metric between the f32 query (never
+ *     quantised) and the decoded row, accumulated in f32.  COSINE stores the
+ *     code of the f32-normalised row and uses it as stored.
+ *   - dg_reconstruct returns the decoded row.  dg_last_scan_pair is 0;
+ *     dg_save writes the DGI2 container with the ranges, dg_save_faiss
+ *     returns DG_ENOT_SUPPORT. */
+typedef enum dg_storage {
+  DG_STORAGE_F32 = 0,
+  DG_STORAGE_F16 = 1,
+  DG_STORAGE_SQ8 = 2
+} dg_storage;
 dg_status dg_set_storage(dg_index* idx, int32_t storage);
 int32_t dg_get_storage(dg_index* idx); /* -1 for NULL */
+/* Inject / read back the per-dimension ranges of an SQ8 index (the analogue
+ * of dg_set_centroids for tests that share a structure with a reference).
+ * Set: SQ8 storage and ntotal == 0, every value finite and vdiff[j] >= 0,
+ * else DG_EINVAL.  Get: DG_ENOT_TRAINED while there are no ranges.  On an
+ * index of other storage both return DG_EINVAL. */
+dg_status dg_set_sq_ranges(dg_index* idx, const float* vmin /* d */,
+                           const float* vdiff /* d */);
+dg_status dg_get_sq_ranges(dg_index* idx, float* vmin /* d */,
+                           float* vdiff /* d */);
 /* The stored row of each id decoded to f32, out[n x d] at the caller's d
  * stride (for COSINE the normalised rows).  FLAT and IVF_FLAT, either
  * storage.  Every id must be live, else DG_ENOT_FOUND and out is untouched;
@@ -576,6 +613,12 @@ dg_index* dg_sharded_shard(dg_sharded* sh, int32_t i);
 /* dg_set_storage on every shard, before any row is added (there is no
  * dg_sharded_reconstruct) */
 dg_status dg_sharded_set_storage(dg_sharded* sh, int32_t storage);
+/* dg_set_sq_ranges on every shard / dg_get_sq_ranges of shard 0.
+ * dg_sharded_train replicates shard 0's ranges bit-identically, like its
+ * centroids. */
+dg_status dg_sharded_set_sq_ranges(dg_sharded* sh, const float* vmin,
+                                   const float* vdiff);
+dg_status dg_sharded_get_sq_ranges(dg_sharded* sh, float* vmin, float* vdiff);
 
 /* ---- wrapper-lifecycle lock (LockWrite/UnlockWrite,
  * vector_index.h:192-193): the exclusive lock the reference wrapper takes
@@ -602,6 +645,9 @@ int dg_last_scan_pair(dg_index* idx);
 /* 1 if the last IVF-Flat search that ran its kernels scanned f16 rows
  * (k_ivf_scan_f16, either candidate flow), 0 otherwise. */
 int dg_last_scan_f16(dg_index* idx);
+/* 1 if the last IVF-Flat search that ran its kernels scanned SQ8 rows
+ * (k_ivf_scan_sq8, either candidate flow), 0 otherwise. */
+int dg_last_scan_sq8(dg_index* idx);
 int dg_device_count(void);
 /* Library self-identification: returns a static string with build arch. */
 const char* dg_build_info(void);
