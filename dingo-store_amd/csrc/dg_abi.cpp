@@ -94,6 +94,14 @@ static bool scan_mfma_enabled() {
   return !(e && e[0] == '0' && e[1] == '\0');
 }
 
+// DG_COARSE_WAVE=0 keeps the coarse probe selection on k_select_dense +
+// k_probe_unpack + k_hist_probes instead of k_coarse_select (A/B switch and
+// tests); read per call likewise.
+static bool coarse_wave_enabled() {
+  const char* e = getenv("DG_COARSE_WAVE");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
 // DG_SCAN_PAIR=0 keeps every query tile on k_ivf_scan_mfma (no pair
 // kernel); 1, 2 or 4 set the pair kernel's grid.y (A/B switch for the
 // measurement in DESIGN.md §Pair scan); anything else is the default.
@@ -2336,6 +2344,35 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     uint64_t* final_tk = (uint64_t*)(probes + (size_t)nq * np);  // nq x k
     const uint8_t* maskp =
         ix->has_mask ? (const uint8_t*)ix->d_list_mask.p : nullptr;
+    // inverted mapping + candidate offsets (reserved ahead of the coarse
+    // step: k_coarse_select counts its probes into inv_counts)
+    size_t inv_bytes = (size_t)nlist * 4 * 3 + ((size_t)nlist + 1) * 12 +
+                       (size_t)nq * np * 8 * 2 + ((size_t)nq + 1) * 8 * 2 +
+                       (size_t)nq * np * 8 + 64;
+    if ((st = dbuf_reserve(ix->ws_inv, inv_bytes, ix->stream, false)) !=
+        DG_OK) {
+      return st;
+    }
+    char* wp = (char*)ix->ws_inv.p;
+    int32_t* inv_counts = (int32_t*)wp;            wp += (size_t)nlist * 4;
+    int32_t* cursors = (int32_t*)wp;               wp += (size_t)nlist * 4;
+    wp += (size_t)nlist * 4;  // (reserved; unit counting now launch-free)
+    int64_t* inv_offsets64 = (int64_t*)wp;         wp += ((size_t)nlist + 1) * 8;
+    int32_t* inv_offsets32 = (int32_t*)wp;         wp += ((size_t)nlist + 1) * 4;
+    int32_t* inv_q = (int32_t*)wp;                 wp += (size_t)nq * np * 4;
+    int32_t* inv_rank = (int32_t*)wp;              wp += (size_t)nq * np * 4;
+    int64_t* qp_off = (int64_t*)wp;                wp += (size_t)nq * np * 8;
+    int64_t* q_total = (int64_t*)wp;               wp += (size_t)nq * 8;
+    int64_t* q_cand_base = (int64_t*)wp;  // nq+1
+    (void)hipMemsetAsync(inv_counts, 0, (size_t)nlist * 4, ix->stream);
+    // one-kernel selection straight to probes (and the probe histogram)
+    // where it applies; DG_COARSE_WAVE=0 keeps k_select_dense +
+    // k_probe_unpack + k_hist_probes
+    const bool cwave = dg_coarse_wave_applies(np, nlist) &&
+                       coarse_wave_enabled();
+    ix->last_coarse_wave = cwave;
+    ix->last_probes = probes;
+    ix->last_probes_n = nq * (int64_t)np;
     if (is_pq && np == nlist) {
       // PQ needs the coarse dots matrix in every case (ADC bias term)
       st = sgemm_dots(ix, dq, nq, (const float*)ix->d_centroids.p, nlist, d,
@@ -2366,62 +2403,47 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
       // this is the single-launch path of round 1
       const int32_t nseg_c = (int32_t)std::min<int64_t>(
           16, std::max<int64_t>(1, nlist / 8192));
-      if (nseg_c > 1) {
+      if (cwave) {
+        dgk::coarse_select(ix->stream, (const float*)ix->ws_dots.p,
+                           (const float*)ix->d_cnorms.p, nq, nlist, np, cmode,
+                           maskp, probes, inv_counts);
+      } else if (nseg_c > 1) {
         dg_dbuf& seg = ix->ws_seg;
-        if ((st = dbuf_reserve(seg,
-                               (size_t)nq * nseg_c * np * 8 +
-                                   (size_t)nq * 2 * 8,
-                               ix->stream, false)) != DG_OK)
+        if ((st = dbuf_reserve(seg, (size_t)nq * nseg_c * np * 8, ix->stream,
+                               false)) != DG_OK)
           return st;
         uint64_t* seg_slab = (uint64_t*)seg.p;
-        int64_t* bt_c = (int64_t*)(seg_slab + (size_t)nq * nseg_c * np);
         dgk::select_dense(ix->stream, (const float*)ix->ws_dots.p,
                           (const float*)ix->d_cnorms.p, nq, nlist, nlist,
                           nseg_c, np, cmode, nullptr, 0, seg_slab,
                           (int64_t)nseg_c * np, 0);
-        dgk::fill_base_total(ix->stream, nq, (int64_t)nseg_c * np, bt_c,
-                             bt_c + nq);
-        dgk::select_u64(ix->stream, seg_slab, bt_c, bt_c + nq, nq, np,
-                        coarse_tk, np);
+        dgk::select_u64_uniform(ix->stream, seg_slab, (int64_t)nseg_c * np,
+                                nq, np, coarse_tk, np);
+        dgk::probe_unpack(ix->stream, coarse_tk, nq, np, maskp, probes);
       } else {
         dgk::select_dense(ix->stream, (const float*)ix->ws_dots.p,
                           (const float*)ix->d_cnorms.p, nq, nlist, nlist, 1,
                           np, cmode, nullptr, 0, coarse_tk, np, 0);
+        dgk::probe_unpack(ix->stream, coarse_tk, nq, np, maskp, probes);
       }
-      dgk::probe_unpack(ix->stream, coarse_tk, nq, np, maskp, probes);
     }
     if (!ix->capturing) (void)hipEventRecord(ix->ev[1], ix->stream);
-
-    // inverted mapping + candidate offsets
-    size_t inv_bytes = (size_t)nlist * 4 * 3 + ((size_t)nlist + 1) * 12 +
-                       (size_t)nq * np * 8 * 2 + ((size_t)nq + 1) * 8 * 2 +
-                       (size_t)nq * np * 8 + 64;
-    if ((st = dbuf_reserve(ix->ws_inv, inv_bytes, ix->stream, false)) !=
-        DG_OK) {
-      return st;
-    }
-    char* wp = (char*)ix->ws_inv.p;
-    int32_t* inv_counts = (int32_t*)wp;            wp += (size_t)nlist * 4;
-    int32_t* cursors = (int32_t*)wp;               wp += (size_t)nlist * 4;
-    wp += (size_t)nlist * 4;  // (reserved; unit counting now launch-free)
-    int64_t* inv_offsets64 = (int64_t*)wp;         wp += ((size_t)nlist + 1) * 8;
-    int32_t* inv_offsets32 = (int32_t*)wp;         wp += ((size_t)nlist + 1) * 4;
-    int32_t* inv_q = (int32_t*)wp;                 wp += (size_t)nq * np * 4;
-    int32_t* inv_rank = (int32_t*)wp;              wp += (size_t)nq * np * 4;
-    int64_t* qp_off = (int64_t*)wp;                wp += (size_t)nq * np * 8;
-    int64_t* q_total = (int64_t*)wp;               wp += (size_t)nq * 8;
-    int64_t* q_cand_base = (int64_t*)wp;  // nq+1
 
     int64_t* sscr = scan_scratch(ix, &st);
     if (st != DG_OK) {
       return st;
     }
-    (void)hipMemsetAsync(inv_counts, 0, (size_t)nlist * 4, ix->stream);
-    dgk::hist_probes(ix->stream, probes, nq, np, nlist, inv_counts);
-    dgk::excl_scan_i32_to_i64(ix->stream, inv_counts, nlist, inv_offsets64,
-                              sscr);
-    dgk::init_cursors(ix->stream, inv_offsets64, nlist + 1, inv_offsets32);
-    dgk::init_cursors(ix->stream, inv_offsets64, nlist, cursors);
+    if (!cwave)
+      dgk::hist_probes(ix->stream, probes, nq, np, nlist, inv_counts);
+    if (dg_inv_offsets_applies(nlist)) {
+      dgk::inv_offsets(ix->stream, inv_counts, nlist, inv_offsets64,
+                       inv_offsets32, cursors);
+    } else {
+      dgk::excl_scan_i32_to_i64(ix->stream, inv_counts, nlist, inv_offsets64,
+                                sscr);
+      dgk::init_cursors(ix->stream, inv_offsets64, nlist + 1, inv_offsets32);
+      dgk::init_cursors(ix->stream, inv_offsets64, nlist, cursors);
+    }
     dgk::scatter_probes(ix->stream, probes, nq, np, nullptr, cursors, inv_q,
                         inv_rank);
     const int32_t chunk_rows = dg_index::kChunkRows;
@@ -2642,10 +2664,8 @@ static dg_status search_core(dg_index* ix, int64_t nq, const float* d_x,
     }
     // select + emit (fused: merge of the per-wave slots, uniform segments)
     if (fused) {
-      dgk::fill_base_total(ix->stream, nq, partial_per_q, q_cand_base,
-                           q_total);
-      dgk::select_u64(ix->stream, (const uint64_t*)ix->ws_partial.p,
-                      q_cand_base, q_total, nq, k, final_tk, k);
+      dgk::select_u64_uniform(ix->stream, (const uint64_t*)ix->ws_partial.p,
+                              partial_per_q, nq, k, final_tk, k);
     } else {
       dgk::select_u64(ix->stream, (const uint64_t*)ix->ws_cand.p, q_cand_base,
                       q_total, nq, k, final_tk, k);
@@ -2732,10 +2752,11 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
     const bool fused_now = scan_fused_enabled();  // captured into the graph
     const bool mfma_now = scan_mfma_enabled();    // likewise
     const int32_t pair_now = scan_pair_py();      // likewise
+    const bool cwave_now = coarse_wave_enabled();  // likewise
     if (ix->graph_exec && ix->graph_nq == (int32_t)nq &&
         ix->graph_k == k && ix->graph_np == nprobe &&
         ix->graph_fused == fused_now && ix->graph_mfma == mfma_now &&
-        ix->graph_pair == pair_now &&
+        ix->graph_pair == pair_now && ix->graph_cwave == cwave_now &&
         ix->graph_gen == gen) {
       DG_HIP_CHECK(hipMemcpyAsync(ix->ws_gq.p, d_x, q_bytes,
                                   hipMemcpyDeviceToDevice, ix->stream));
@@ -2791,6 +2812,7 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
           ix->graph_fused = fused_now;
           ix->graph_mfma = mfma_now;
           ix->graph_pair = pair_now;
+          ix->graph_cwave = cwave_now;
           // capture itself allocates nothing (warm run sized buffers),
           // so gen2 still describes the captured pointers
           ix->graph_gen = gen2;
@@ -3338,6 +3360,30 @@ extern "C" int dg_last_scan_fused(dg_index* ix) {
   if (!ix) return 0;
   std::lock_guard sg(ix->search_mu);
   return ix->last_scan_fused ? 1 : 0;
+}
+
+extern "C" int dg_last_coarse_wave(dg_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard sg(ix->search_mu);
+  return ix->last_coarse_wave ? 1 : 0;
+}
+
+extern "C" int64_t dg_last_probes(dg_index* ix, int32_t* out, int64_t n) {
+  if (!ix || n < 0 || (n > 0 && !out)) {
+    dg_set_error("bad dg_last_probes args");
+    return -1;
+  }
+  DeviceGuard g(ix->device);
+  std::lock_guard sg(ix->search_mu);
+  if (!ix->last_probes) return 0;
+  const int64_t m = std::min(n, ix->last_probes_n);
+  if (m > 0 && (hipStreamSynchronize(ix->stream) != hipSuccess ||
+                hipMemcpy(out, ix->last_probes, (size_t)m * 4,
+                          hipMemcpyDeviceToHost) != hipSuccess)) {
+    dg_set_error("dg_last_probes copy failed");
+    return -1;
+  }
+  return ix->last_probes_n;
 }
 
 extern "C" int dg_last_scan_pair(dg_index* ix) {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/dingo_gpu.h"
+#include "dg_coarse_wave.h"
 #include "dg_scan_split.h"
 
 #define DG_HIP_CHECK(expr)                                              \
@@ -239,6 +240,9 @@ struct dg_index {
   bool last_scan_mfma = false;   // ... and whether it was k_ivf_scan_mfma
   bool last_scan_pair = false;   // ... and whether k_ivf_scan_mfma2 ran too
   dg_dbuf ws_qimage;             // its operand image of the queries
+  bool last_coarse_wave = false;  // the last IVF search ran k_coarse_select
+  const int32_t* last_probes = nullptr;  // its probes array (in ws_probes)
+  int64_t last_probes_n = 0;             // ... and its nq * np entries
 
   // timing
   hipEvent_t ev[12] = {};
@@ -254,6 +258,7 @@ struct dg_index {
   bool graph_fused = false;  // DG_SCAN_FUSED state the graph was captured in
   bool graph_mfma = false;   // DG_SCAN_MFMA state, likewise
   int32_t graph_pair = 0;    // DG_SCAN_PAIR state, likewise
+  bool graph_cwave = false;  // DG_COARSE_WAVE state, likewise
   uint64_t graph_gen = 0;   // generation the graph was captured at
   uint64_t index_gen = 1;   // bumped on finalize/mutation/buffer growth
   dg_dbuf ws_gq, ws_gout;   // fixed staging: queries in, dist+ids out
@@ -302,6 +307,21 @@ void gather_rows_by_index(hipStream_t s, const float* src, const int64_t* idx,
                           int64_t n, int32_t d, float* dst);
 void fill_base_total(hipStream_t s, int64_t nq, int64_t len, int64_t* base,
                      int64_t* total);
+// select_u64 over uniform segments: query q's candidates are the len entries
+// from cand + q * len (no base / total arrays)
+void select_u64_uniform(hipStream_t s, const uint64_t* cand, int64_t len,
+                        int64_t nq, int32_t k, uint64_t* out,
+                        int64_t out_stride);
+// coarse top-np of dots[nq][nlist] straight to probes[nq][np] (ascending
+// packed key, masked lists -1), counting every probe >= 0 into counts, which
+// the caller has zeroed.  Needs dg_coarse_wave_applies(np, nlist).
+void coarse_select(hipStream_t s, const float* dots, const float* cnorms,
+                   int64_t nq, int32_t nlist, int32_t np, int mode,
+                   const uint8_t* mask, int32_t* probes, int32_t* counts);
+// exclusive scan of counts[nlist] to off64 / off32 (nlist + 1 entries) and
+// cursors (nlist) in one block.  Needs dg_inv_offsets_applies(nlist).
+void inv_offsets(hipStream_t s, const int32_t* counts, int32_t nlist,
+                 int64_t* off64, int32_t* off32, int32_t* cursors);
 void tombstone(hipStream_t s, const int64_t* pos, int64_t n, int64_t* ids);
 // binary (Hamming) indexes: packed u32 words, wp words per row
 // out[nq x cols] (row stride ld) = popcount(X[q] ^ Y[c]) as exact f32

@@ -203,6 +203,18 @@ __device__ void topk_merge_block(uint64_t* lds, int32_t k, int32_t cnt,
   }
 }
 
+// The selection key of a dense score: mode 0 key=score, 1 key=cnorm-2*score,
+// 2 key=-score.  One definition for k_select_dense and k_coarse_select, so
+// that floating-point contraction gives both the same bits.
+__device__ __forceinline__ float select_key_v(int mode, float cn, float s) {
+  return (mode == 0) ? s : (mode == 1) ? cn - 2.0f * s : -s;
+}
+__device__ __forceinline__ float select_key(int mode,
+                                            const float* __restrict__ cn,
+                                            int64_t c, float s) {
+  return select_key_v(mode, mode == 1 ? cn[c] : 0.0f, s);
+}
+
 // dense scores row scan: mode 0 key=score, 1 key=cnorm[col]-2*score,
 // 2 key=-score.  col_base added to the packed payload (and is the global
 // column index for the bitmap); cnorms is indexed by the local column.
@@ -232,8 +244,7 @@ __global__ void k_select_dense(const float* __restrict__ scores,
       int64_t g = col_base + seg_start + c;
       if (!((bitmap[g >> 5] >> (g & 31)) & 1)) continue;
     }
-    float s = sr[c];
-    float key = (mode == 0) ? s : (mode == 1) ? cn[c] - 2.0f * s : -s;
+    float key = select_key(mode, cn, c, sr[c]);
     topk_insert(mine, cnt, k,
                 pack_cand(key, (uint32_t)(col_base + seg_start + c)));
   }
@@ -241,17 +252,20 @@ __global__ void k_select_dense(const float* __restrict__ scores,
                    out + row * out_stride + out_offset + blockIdx.y * k);
 }
 
-// candidate (u64) segment scan per query
+// candidate (u64) segment scan per query.  ulen >= 0: every query's segment
+// is ulen long and starts at q * ulen (base and total are not read).
 __global__ void k_select_u64(const uint64_t* __restrict__ cand,
                              const int64_t* __restrict__ base,
-                             const int64_t* __restrict__ total, int64_t nq,
-                             int32_t k, uint64_t* __restrict__ out,
+                             const int64_t* __restrict__ total, int64_t ulen,
+                             int64_t nq, int32_t k,
+                             uint64_t* __restrict__ out,
                              int64_t out_stride) {
   extern __shared__ uint64_t lds[];
   int64_t q = blockIdx.x;
   if (q >= nq) return;
-  const uint64_t* seg = cand + (base ? base[q] : q * total[0]);
-  int64_t len = base ? total[q] : total[0];
+  const uint64_t* seg =
+      cand + (ulen >= 0 ? q * ulen : base ? base[q] : q * total[0]);
+  int64_t len = ulen >= 0 ? ulen : base ? total[q] : total[0];
   uint64_t* mine = lds + (size_t)threadIdx.x * k;
   int32_t cnt = 0;
   for (int64_t i = threadIdx.x; i < len; i += blockDim.x)
@@ -365,6 +379,166 @@ __global__ void k_scatter_probes(const int32_t* __restrict__ probes,
   int32_t pos = atomicAdd(&cursors[l], 1);
   inv_q[pos] = (int32_t)(i / nprobe);
   inv_rank[pos] = (int32_t)(i % nprobe);
+}
+
+// ---------- coarse probe selection in one kernel ----------
+// One block of 4 waves per query picks the np smallest packed keys
+// (enc_f32(key) << 32 | list) of a row of nlist coarse scores and writes the
+// probe list itself, in ascending key order (DESIGN.md §Coarse probe
+// selection).  It is an MSB-first radix select over the 64-bit packed key,
+// one byte per pass:
+//   - a pass histograms byte b of the keys whose higher bytes equal the
+//     prefix chosen so far (256 LDS counters), wave 0 scans the counters and
+//     finds the bin that holds the need-th smallest, which extends the
+//     prefix; keys below the prefix are in for good;
+//   - the packed keys of a row are distinct (the list id is part of them), so
+//     a pass whose chosen bin holds exactly `need` keys ends the select: the
+//     np keys with (key >> 8b) <= (prefix >> 8b) are the answer.  Byte 0 always
+//     ends it.  With distinct scores that is the 3rd or 4th pass; the list-id
+//     bytes are only reached through equal scores at the np-th place, and
+//     those above nlist's width are skipped (they are zero in every key);
+//   - the np survivors go to LDS in arrival order and each of the first np
+//     threads ranks its own by counting the smaller ones (np <= 128 broadcast
+//     reads), writes probes[q][rank] (masked lists as -1) and counts the
+//     probe into the per-list histogram that k_hist_probes would build.
+// The row is re-read from L2 in every pass (16 KB at nlist 4096) with float4
+// loads when rows are 16-byte aligned (nlist % 4 == 0).  A wave whose lanes
+// all hit one counter (the exponent byte, as a rule) adds once.
+__global__ void __launch_bounds__(kCoarseWaveThreads)
+k_coarse_select(const float* __restrict__ dots,
+                const float* __restrict__ cnorms, int32_t nlist, int32_t np,
+                int mode, const uint8_t* __restrict__ mask,
+                int32_t* __restrict__ probes, int32_t* __restrict__ counts) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint64_t surv[kCoarseWaveMaxNp];
+  __shared__ uint32_t s_bin, s_need, s_done, s_cnt;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+  const int64_t q = blockIdx.x;
+  const float* row = dots + q * nlist;
+  const int32_t n4 = (nlist & 3) == 0 ? nlist >> 2 : 0;
+
+  auto for_each_key = [&](auto&& f) {
+    for (int32_t g = tid; g < n4; g += kCoarseWaveThreads) {
+      const float4 s = ((const float4*)row)[g];
+      float4 c = {0.f, 0.f, 0.f, 0.f};
+      if (mode == 1) c = ((const float4*)cnorms)[g];
+      const uint32_t col = 4u * (uint32_t)g;
+      f(pack_cand(select_key_v(mode, c.x, s.x), col));
+      f(pack_cand(select_key_v(mode, c.y, s.y), col + 1));
+      f(pack_cand(select_key_v(mode, c.z, s.z), col + 2));
+      f(pack_cand(select_key_v(mode, c.w, s.w), col + 3));
+    }
+    for (int32_t c = 4 * n4 + tid; c < nlist; c += kCoarseWaveThreads)
+      f(pack_cand(select_key(mode, cnorms, c, row[c]), (uint32_t)c));
+  };
+
+  uint64_t prefix = 0;
+  uint32_t need = (uint32_t)np;
+  int shift = 56;
+  for (int b = 7; b >= 0; b--) {
+    // list-id bytes above nlist's width are zero in every key
+    if (b > 0 && b < 4 && ((uint32_t)(nlist - 1) >> (8 * b)) == 0) continue;
+    shift = 8 * b;
+    hist[tid] = 0;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    for_each_key([&](uint64_t key) {
+      // b == 7 has no higher bytes (and a 64-bit shift is undefined)
+      if (b == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8))) {
+        const uint32_t bin = (uint32_t)(key >> shift) & 255u;
+        const uint32_t first = __builtin_amdgcn_readfirstlane(bin);
+        const uint64_t act = __ballot(1);
+        if (__ballot(bin == first) == act) {
+          if (lane == __ffsll((long long)act) - 1)
+            atomicAdd(&hist[first], (uint32_t)__popcll(act));
+        } else {
+          atomicAdd(&hist[bin], 1u);
+        }
+      }
+    });
+    __syncthreads();
+    if (tid < WAVE) {
+      const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1],
+                     h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+      const uint32_t sum = h0 + h1 + h2 + h3;
+      uint32_t incl = sum;
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const uint32_t t = __shfl_up(incl, off, WAVE);
+        if (lane >= off) incl += t;
+      }
+      const uint32_t excl = incl - sum;
+      if (excl < need && need <= incl) {  // exactly one lane
+        uint32_t r = need - excl, j = 0, hj = h0;
+        if (r > hj) { r -= hj; j = 1; hj = h1; }
+        if (r > hj) { r -= hj; j = 2; hj = h2; }
+        if (r > hj) { r -= hj; j = 3; hj = h3; }
+        s_bin = 4 * lane + j;
+        s_need = r;
+        s_done = (hj == r) ? 1u : 0u;
+      }
+    }
+    __syncthreads();
+    prefix |= (uint64_t)s_bin << shift;
+    need = s_need;
+    if (s_done) break;
+    // the next pass's stores to hist and s_* follow its own barrier-separated
+    // reads: hist is reset before the first barrier of the pass, after every
+    // thread has passed the barrier above; s_* are written after the second
+  }
+
+  // exactly np keys have (key >> shift) <= (prefix >> shift)
+  const uint64_t limit = prefix >> shift;
+  for_each_key([&](uint64_t key) {
+    if ((key >> shift) <= limit) {
+      const uint32_t slot = atomicAdd(&s_cnt, 1u);
+      if (slot < (uint32_t)np) surv[slot] = key;
+    }
+  });
+  __syncthreads();
+  if (tid < np) {
+    const uint64_t key = surv[tid];
+    int32_t rank = 0;
+    for (int32_t j = 0; j < np; j++) rank += surv[j] < key ? 1 : 0;
+    int32_t l = (int32_t)(key & 0xffffffffu);
+    if (mask && !mask[l]) l = -1;  // list-sharding ownership
+    probes[q * np + rank] = l;
+    if (l >= 0) atomicAdd(&counts[l], 1);
+  }
+}
+
+// exclusive scan of the per-list probe counts in one block: inv_offsets as
+// int64 and int32 (nlist + 1 entries, the last is the total) and the scatter
+// cursors (nlist entries), which start at the offsets.  Thread t owns the
+// dg_inv_offsets_per_thread(nlist) lists from t * per on.
+__global__ void __launch_bounds__(kInvOffsetsThreads)
+k_inv_offsets(const int32_t* __restrict__ counts, int32_t nlist,
+              int64_t* __restrict__ off64, int32_t* __restrict__ off32,
+              int32_t* __restrict__ cursors) {
+  __shared__ int64_t wsum[kInvOffsetsThreads / WAVE];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+  const int32_t per = dg_inv_offsets_per_thread(nlist);
+  const int32_t lo = min(tid * per, nlist), hi = min(lo + per, nlist);
+  int64_t sum = 0;
+  for (int32_t i = lo; i < hi; i++) sum += counts[i];
+  int64_t incl = sum;
+  for (int off = 1; off < WAVE; off <<= 1) {
+    const int64_t t = __shfl_up(incl, off, WAVE);
+    if (lane >= off) incl += t;
+  }
+  if (lane == WAVE - 1) wsum[w] = incl;
+  __syncthreads();
+  int64_t run = incl - sum;
+  for (int i = 0; i < w; i++) run += wsum[i];
+  for (int32_t i = lo; i < hi; i++) {
+    off64[i] = run;
+    off32[i] = (int32_t)run;
+    cursors[i] = (int32_t)run;
+    run += counts[i];
+  }
+  if (tid == kInvOffsetsThreads - 1) {  // its run is the total
+    off64[nlist] = run;
+    off32[nlist] = (int32_t)run;
+  }
 }
 
 __global__ void k_cand_offsets(const int32_t* __restrict__ probes, int64_t nq,
@@ -4091,7 +4265,31 @@ void select_u64(hipStream_t s, const uint64_t* cand, const int64_t* base,
   int T = select_threads(k);
   size_t lds = 2ull * T * k * 8;
   hipLaunchKernelGGL(k_select_u64, dim3((uint32_t)nq), dim3(T), lds, s, cand,
-                     base, total, nq, k, out, out_stride);
+                     base, total, (int64_t)-1, nq, k, out, out_stride);
+}
+
+void select_u64_uniform(hipStream_t s, const uint64_t* cand, int64_t len,
+                        int64_t nq, int32_t k, uint64_t* out,
+                        int64_t out_stride) {
+  int T = select_threads(k);
+  size_t lds = 2ull * T * k * 8;
+  hipLaunchKernelGGL(k_select_u64, dim3((uint32_t)nq), dim3(T), lds, s, cand,
+                     (const int64_t*)nullptr, (const int64_t*)nullptr, len,
+                     nq, k, out, out_stride);
+}
+
+void coarse_select(hipStream_t s, const float* dots, const float* cnorms,
+                   int64_t nq, int32_t nlist, int32_t np, int mode,
+                   const uint8_t* mask, int32_t* probes, int32_t* counts) {
+  hipLaunchKernelGGL(k_coarse_select, dim3((uint32_t)nq),
+                     dim3(kCoarseWaveThreads), 0, s, dots, cnorms, nlist, np,
+                     mode, mask, probes, counts);
+}
+
+void inv_offsets(hipStream_t s, const int32_t* counts, int32_t nlist,
+                 int64_t* off64, int32_t* off32, int32_t* cursors) {
+  hipLaunchKernelGGL(k_inv_offsets, dim3(1), dim3(kInvOffsetsThreads), 0, s,
+                     counts, nlist, off64, off32, cursors);
 }
 
 void emit_results(hipStream_t s, const uint64_t* topk,

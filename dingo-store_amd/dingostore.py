@@ -690,6 +690,27 @@ class Index:
         l.dg_last_scan_pair.restype = C.c_int
         return bool(l.dg_last_scan_pair(self.h))
 
+    def last_coarse_wave(self):
+        """True if the last IVF search that ran its kernels selected its
+        probes with k_coarse_select; False with DG_COARSE_WAVE=0, nprobe
+        above the kernel's cap or nprobe >= nlist (dg_last_coarse_wave)."""
+        l = lib()
+        l.dg_last_coarse_wave.argtypes = [C.c_void_p]
+        l.dg_last_coarse_wave.restype = C.c_int
+        return bool(l.dg_last_coarse_wave(self.h))
+
+    def last_probes(self):
+        """The last IVF search's probes, int32 in selection order, -1 for a
+        masked list, as one flat array of nq * nprobe entries
+        (dg_last_probes; a debugging accessor)."""
+        l = lib()
+        l.dg_last_probes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        l.dg_last_probes.restype = C.c_int64
+        out = np.empty(max(l.dg_last_probes(self.h, None, 0), 0), np.int32)
+        if l.dg_last_probes(self.h, out.ctypes.data, out.size) != out.size:
+            raise DgError("dg_last_probes: " + last_error())
+        return out
+
     def stats(self):
         s = _Stats()
         _check(lib().dg_stats(self.h, C.byref(s)), "dg_stats")

@@ -648,6 +648,17 @@ int dg_last_scan_f16(dg_index* idx);
 /* 1 if the last IVF-Flat search that ran its kernels scanned SQ8 rows
  * (k_ivf_scan_sq8, either candidate flow), 0 otherwise. */
 int dg_last_scan_sq8(dg_index* idx);
+/* 1 if the last IVF search that ran its kernels (any IVF kind) selected its
+ * probes with the one-kernel radix select (k_coarse_select), 0 if it ran
+ * k_select_dense + k_probe_unpack: DG_COARSE_WAVE=0, nprobe > 128, or
+ * nprobe >= nlist (every list probed, nothing selected). */
+int dg_last_coarse_wave(dg_index* idx);
+/* Debugging accessor: the probes of the last IVF search, [nq][nprobe] list
+ * ids in selection order (best first), -1 where the list mask removed one.
+ * Waits for the index's stream, copies min(n, nq * nprobe) entries to the
+ * host array out and returns nq * nprobe (so n = 0, out = NULL asks for the
+ * size); 0 before the first IVF search, -1 on error. */
+int64_t dg_last_probes(dg_index* idx, int32_t* out, int64_t n);
 int dg_device_count(void);
 /* Library self-identification: returns a static string with build arch. */
 const char* dg_build_info(void);
