@@ -407,11 +407,17 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
     }
   }
   if (desc.kind != DG_INDEX_FLAT && desc.kind != DG_INDEX_IVF_FLAT &&
-      desc.kind != DG_INDEX_IVF_PQ && !is_bin) {
+      desc.kind != DG_INDEX_IVF_PQ && !is_bin &&
+      !dg_kind_is_hnsw(desc.kind)) {
     dg_set_error("bad kind %d", desc.kind);
     return DG_EINVAL;
   }
-  if (!dg_kind_is_flat(desc.kind) && desc.nlist <= 0)
+  if (dg_kind_is_hnsw(desc.kind)) {
+    // nlist, pq_m, pq_nbits mean nothing here; the graph is host-built, so
+    // there is no device store to reserve either
+    desc.nlist = desc.pq_m = desc.pq_nbits = 0;
+    desc.reserve = 0;
+  } else if (!dg_kind_is_flat(desc.kind) && desc.nlist <= 0)
     desc.nlist = 2048;  // kCreateIvfFlatParamNcentroids, constant.h:177
   if (dg_device_count() == 0) {
     dg_set_error("no HIP device (the GPU path has no CPU fallback)");
@@ -451,6 +457,14 @@ extern "C" dg_status dg_index_create(dg_index** out, const dg_index_desc* dp) {
   ix->events_ready = true;
   (void)hipHostMalloc((void**)&ix->h_pinned, 64);
   if (dg_kind_is_flat(desc.kind)) ix->trained = true;
+  if (dg_kind_is_hnsw(desc.kind)) {
+    ix->trained = true;  // dg_train is a no-op for this kind
+    const dg_status hst = dg_hnsw_create_state(ix);
+    if (hst != DG_OK) {
+      dg_index_destroy(ix);
+      return hst;
+    }
+  }
   if (desc.reserve > 0) {  // capacity hint: avoids grow-copies during add
     // PQ never stores raw vectors (codes only); others reserve the vector
     // store up front
@@ -484,6 +498,7 @@ extern "C" void dg_index_destroy(dg_index* ix) {
   // batched callers drain first; their staging goes with the batcher
   dg_batcher_destroy(ix->batcher.exchange(nullptr));
   (void)hipStreamSynchronize(ix->stream);
+  dg_hnsw_destroy_state(ix);
   for (auto b :
        {&ix->d_vectors, &ix->d_ids, &ix->d_assign, &ix->d_centroids,
         &ix->d_cnorms, &ix->d_csr_offsets, &ix->d_csr_vectors, &ix->d_csr_ids,
@@ -511,7 +526,7 @@ extern "C" dg_status dg_set_centroids(dg_index* ix, int32_t nlist,
                                       const float* centroids) {
   if (!ix || !centroids) return DG_EINVAL;
   if (!entry_matches(ix, false, "dg_set_centroids")) return DG_EINVAL;
-  if (ix->desc.kind == DG_INDEX_FLAT) {
+  if (ix->desc.kind == DG_INDEX_FLAT || dg_kind_is_hnsw(ix->desc.kind)) {
     dg_set_error("set_centroids on non-IVF index");
     return DG_EINVAL;
   }
@@ -547,7 +562,8 @@ extern "C" dg_status dg_set_centroids(dg_index* ix, int32_t nlist,
 extern "C" dg_status dg_get_centroids(dg_index* ix, float* out) {
   if (!ix || !out) return DG_EINVAL;
   if (!entry_matches(ix, false, "dg_get_centroids")) return DG_EINVAL;
-  if (!ix->trained || ix->desc.kind == DG_INDEX_FLAT) {
+  if (!ix->trained || ix->desc.kind == DG_INDEX_FLAT ||
+      dg_kind_is_hnsw(ix->desc.kind)) {
     dg_set_error("not trained");
     return DG_ENOT_TRAINED;
   }
@@ -972,6 +988,7 @@ extern "C" dg_status dg_train(dg_index* ix, int64_t n, const float* x) {
   }
   if (!entry_matches(ix, false, "dg_train")) return DG_EINVAL;
   if (ix->desc.kind == DG_INDEX_FLAT) return DG_OK;  // Flat needs no train
+  if (dg_kind_is_hnsw(ix->desc.kind)) return DG_OK;  // nor does the graph
   std::unique_lock lk(ix->rw);
   // an SQ8 index also needs its ranges; with centroids present only those
   const bool need_ranges =
@@ -1224,6 +1241,8 @@ static dg_status add_impl(dg_index* ix, int64_t n, const int64_t* ids,
   }
   if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
   const float* x = (const float*)xv;  // float kinds
+  if (dg_kind_is_hnsw(ix->desc.kind))
+    return dg_hnsw_add(ix, n, ids, x, x_on_device, /*upsert=*/false);
   std::unique_lock lk(ix->rw);
   if (!ix->is_ready()) {
     dg_set_error("IVF index not trained (EVECTOR_NOT_TRAIN)");
@@ -1478,6 +1497,10 @@ extern "C" dg_status dg_add_device(dg_index* ix, int64_t n,
 
 extern "C" dg_status dg_export_assign(dg_index* ix, int32_t* out) {
   if (!ix || !out) return DG_EINVAL;
+  if (dg_kind_is_hnsw(ix->desc.kind)) {
+    dg_set_error("dg_export_assign: an HNSW index has no coarse lists");
+    return DG_EINVAL;
+  }
   std::shared_lock lk(ix->rw);
   DeviceGuard g(ix->device);
   if (ix->ntotal == 0) return DG_OK;
@@ -1488,6 +1511,7 @@ extern "C" dg_status dg_export_assign(dg_index* ix, int32_t* out) {
 
 extern "C" dg_status dg_remove(dg_index* ix, int64_t n, const int64_t* ids) {
   if (!ix || !ids || n <= 0) return DG_EINVAL;
+  if (dg_kind_is_hnsw(ix->desc.kind)) return dg_hnsw_remove(ix, n, ids);
   std::unique_lock lk(ix->rw);
   // all must exist, else nothing removed (ivf_flat.cc:177-186)
   for (int64_t i = 0; i < n; i++)
@@ -1524,6 +1548,7 @@ extern "C" dg_status dg_remove(dg_index* ix, int64_t n, const int64_t* ids) {
 }
 
 bool dg_contains_id(dg_index* ix, int64_t id) {
+  if (dg_kind_is_hnsw(ix->desc.kind)) return dg_hnsw_contains_id(ix, id);
   std::shared_lock lk(ix->rw);
   return ix->id_count.count(id) != 0;
 }
@@ -1540,6 +1565,11 @@ extern "C" dg_status dg_set_storage(dg_index* ix, int32_t storage) {
     dg_set_error("dg_set_storage: binary indexes store packed bits");
     return DG_EINVAL;
   }
+  if (dg_kind_is_hnsw(ix->desc.kind))  // nothing to re-reserve or invalidate
+    return storage == DG_STORAGE_F32
+               ? DG_OK
+               : (dg_set_error("DG_INDEX_HNSW stores f32 rows only"),
+                  DG_ENOT_SUPPORT);
   if (storage != DG_STORAGE_F32 && ix->desc.kind != DG_INDEX_IVF_FLAT) {
     dg_set_error("DG_STORAGE_F16 and DG_STORAGE_SQ8 are implemented for "
                  "DG_INDEX_IVF_FLAT only");
@@ -1602,6 +1632,8 @@ extern "C" dg_status dg_reconstruct(dg_index* ix, int64_t n,
     dg_set_error("dg_reconstruct: IVF-PQ keeps codes, not rows");
     return DG_ENOT_SUPPORT;
   }
+  if (dg_kind_is_hnsw(ix->desc.kind))
+    return dg_hnsw_reconstruct(ix, n, ids, out);
   std::shared_lock lk(ix->rw);
   for (int64_t i = 0; i < n; i++)
     if (!ix->id_count.count(ids[i])) {
@@ -1665,6 +1697,8 @@ static dg_status upsert_impl(dg_index* ix, int64_t n, const int64_t* ids,
                              const char* fn) {
   if (!ix || !ids || !x || n <= 0) return DG_EINVAL;
   if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
+  if (dg_kind_is_hnsw(ix->desc.kind))
+    return dg_hnsw_add(ix, n, ids, (const float*)x, false, /*upsert=*/true);
   std::vector<int64_t> existing;
   {
     std::shared_lock lk(ix->rw);
@@ -1725,6 +1759,10 @@ extern "C" dg_status dg_upsert_binary(dg_index* ix, int64_t n,
 
 extern "C" dg_status dg_set_list_mask(dg_index* ix, const uint8_t* mask) {
   if (!ix) return DG_EINVAL;
+  if (dg_kind_is_hnsw(ix->desc.kind)) {
+    dg_set_error("dg_set_list_mask: an HNSW index has no lists");
+    return DG_ENOT_SUPPORT;
+  }
   std::unique_lock lk(ix->rw);
   DeviceGuard g(ix->device);
   // a captured small-batch graph holds the mask pointer it was captured
@@ -2695,6 +2733,9 @@ static dg_status search_device_impl(dg_index* ix, int64_t nq,
     return DG_EINVAL;
   }
   if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
+  if (dg_kind_is_hnsw(ix->desc.kind))  // nprobe is ignored, no graph replay
+    return dg_search_hnsw_device(ix, nq, d_x, k, 0, filter, d_out_dist,
+                                 d_out_ids);
   if (binary_entry && nq > kMaxScanLen) {
     dg_set_error("nq %lld > %d per call unsupported", (long long)nq,
                  kMaxScanLen);
@@ -2863,13 +2904,19 @@ static dg_status search_host_impl(dg_index* ix, int64_t nq, const void* x,
                                   size_t x_row_bytes, int32_t k,
                                   int32_t nprobe, const dg_filter* filter,
                                   float* out_dist, int64_t* out_ids,
-                                  bool binary_entry, const char* fn) {
+                                  bool binary_entry, const char* fn,
+                                  int32_t hnsw_ef = 0) {
   if (!ix || !x || !out_dist || !out_ids || nq <= 0) {
     dg_set_error("bad search args");
     return DG_EINVAL;
   }
   if (!entry_matches(ix, binary_entry, fn)) return DG_EINVAL;
   if (k <= 0) return DG_OK;
+  const bool hnsw = dg_kind_is_hnsw(ix->desc.kind);
+  if (hnsw) {  // refuse before the staging is sized from k
+    const dg_status hst = dg_hnsw_check_search_args(k, hnsw_ef);
+    if (hst != DG_OK) return hst;
+  }
   DeviceGuard g(ix->device);
   // upload queries, run device path, download (per-thread staging keyed by
   // the index's device)
@@ -2890,9 +2937,12 @@ static dg_status search_host_impl(dg_index* ix, int64_t nq, const void* x,
     DG_HIP_CHECK(hipMemcpyAsync(t_in.p, x, (size_t)nq * x_row_bytes,
                                 hipMemcpyHostToDevice, ix->stream));
   }
-  st = search_device_impl(ix, nq, (const float*)t_in.p, k, nprobe, filter,
-                          (float*)t_dist.p, (int64_t*)t_ids.p, binary_entry,
-                          fn);
+  st = hnsw ? dg_search_hnsw_device(ix, nq, (const float*)t_in.p, k, hnsw_ef,
+                                    filter, (float*)t_dist.p,
+                                    (int64_t*)t_ids.p)
+            : search_device_impl(ix, nq, (const float*)t_in.p, k, nprobe,
+                                 filter, (float*)t_dist.p, (int64_t*)t_ids.p,
+                                 binary_entry, fn);
   if (st != DG_OK) return st;
   std::shared_lock cl(ix->capture_mu);
   DG_HIP_CHECK(hipMemcpyAsync(out_dist, t_dist.p, (size_t)nq * k * 4,
@@ -2900,7 +2950,16 @@ static dg_status search_host_impl(dg_index* ix, int64_t nq, const void* x,
   DG_HIP_CHECK(hipMemcpyAsync(out_ids, t_ids.p, (size_t)nq * k * 8,
                               hipMemcpyDeviceToHost, ix->stream));
   DG_HIP_CHECK(hipStreamSynchronize(ix->stream));
-  return DG_OK;
+  return hnsw ? dg_hnsw_after_sync(ix) : DG_OK;
+}
+
+dg_status dg_hnsw_search_host(dg_index* ix, int64_t nq, const float* x,
+                              int32_t k, int32_t ef_search,
+                              const dg_filter* filter, float* out_dist,
+                              int64_t* out_ids) {
+  return search_host_impl(ix, nq, x, (size_t)ix->d_user * 4, k, 0, filter,
+                          out_dist, out_ids, false, "dg_search_hnsw",
+                          ef_search);
 }
 
 extern "C" dg_status dg_search(dg_index* ix, int64_t nq, const float* x,
@@ -2944,6 +3003,10 @@ extern "C" dg_status dg_range_search(dg_index* ix, int64_t nq, const float* x,
   if (ix->is_bin) {
     dg_set_error("dg_range_search called on a binary index: use "
                  "dg_range_search_binary");
+    return DG_ENOT_SUPPORT;
+  }
+  if (dg_kind_is_hnsw(ix->desc.kind)) {
+    dg_set_error("dg_range_search: not offered for DG_INDEX_HNSW");
     return DG_ENOT_SUPPORT;
   }
   DeviceGuard g(ix->device);
@@ -3055,6 +3118,11 @@ extern "C" dg_status dg_save(dg_index* ix, const char* path) {
   if (ix->is_bin) {
     dg_set_error("container v1 does not hold binary indexes: use "
                  "dg_save_faiss_binary");
+    return DG_ENOT_SUPPORT;
+  }
+  if (dg_kind_is_hnsw(ix->desc.kind)) {
+    dg_set_error("container v1 does not hold HNSW indexes: use "
+                 "dg_save_hnswlib");
     return DG_ENOT_SUPPORT;
   }
   std::shared_lock lk(ix->rw);
@@ -3406,6 +3474,7 @@ extern "C" int dg_last_scan_mfma(dg_index* ix) {
 
 extern "C" dg_status dg_stats(dg_index* ix, dg_stats_out* out) {
   if (!ix || !out) return DG_EINVAL;
+  if (dg_kind_is_hnsw(ix->desc.kind)) return dg_hnsw_stats(ix, out);
   std::shared_lock lk(ix->rw);
   DeviceGuard g(ix->device);
   memset(out, 0, sizeof(*out));

@@ -243,6 +243,11 @@ static dg_status search_batched_impl(dg_index* ix, int64_t nq, const void* x,
   if (!x || !out_dist || !out_ids || nq <= 0 || k <= 0 || k > 2048 ||
       ix->is_bin != binary)
     return direct();
+  if (dg_kind_is_hnsw(ix->desc.kind)) {
+    // one wave per query already: a graph search gains nothing from a merge
+    (void)b->core.note_bypass(nq);
+    return direct();
+  }
   dgb::Key key;
   if (filter && filter->kind != DG_FILTER_NONE) {
     if (filter->kind != DG_FILTER_RANGE) {

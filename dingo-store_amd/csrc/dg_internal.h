@@ -109,6 +109,15 @@ static inline int32_t dg_pq_code_size(const dg_index_desc& d) {
   return d.pq_m * d.pq_nbits / 8;
 }
 
+// DG_INDEX_HNSW keeps its graph, its host rows and its device mirror in a
+// state of its own (dg_hnsw.cpp); the Flat / IVF members of dg_index below
+// stay unused for that kind, except the stream, the events, the counts and
+// the locks.
+struct dg_hnsw_state;
+static inline bool dg_kind_is_hnsw(int32_t kind) {
+  return kind == DG_INDEX_HNSW;
+}
+
 struct dg_stage_times {
   double coarse_ms = 0, scan_ms = 0, select_ms = 0, total_ms = 0;
   // cumulative since last reset (for bench averaging)
@@ -218,6 +227,9 @@ struct dg_index {
   dg_dbuf d_list_mask;      // [nlist] u8, empty = all owned
   bool has_mask = false;
 
+  // DG_INDEX_HNSW: everything but the members named at dg_hnsw_state above
+  dg_hnsw_state* hnsw = nullptr;
+
   // id -> present (host, duplicate detection / remove)
   std::unordered_map<int64_t, int32_t> id_count;
 
@@ -283,8 +295,58 @@ struct dg_index {
   std::shared_mutex capture_mu;
 };
 
+// ---- DG_INDEX_HNSW (dg_hnsw.cpp): what the generic entry points of
+// dg_abi.cpp, dg_batch.cpp and dg_shard.cpp dispatch to ----
+dg_status dg_hnsw_create_state(dg_index* ix);
+void dg_hnsw_destroy_state(dg_index* ix);
+dg_status dg_hnsw_add(dg_index* ix, int64_t n, const int64_t* ids,
+                      const float* x, bool x_on_device, bool upsert);
+dg_status dg_hnsw_remove(dg_index* ix, int64_t n, const int64_t* ids);
+dg_status dg_hnsw_reconstruct(dg_index* ix, int64_t n, const int64_t* ids,
+                              float* out);
+dg_status dg_hnsw_stats(dg_index* ix, dg_stats_out* out);
+bool dg_hnsw_contains_id(dg_index* ix, int64_t id);
+// the host form of the search (dg_abi.cpp: it owns the per-thread staging),
+// and what it calls after its synchronise: DG_EINTERNAL if a wave of the
+// last search raised the kernel's flag
+dg_status dg_hnsw_search_host(dg_index* ix, int64_t nq, const float* x,
+                              int32_t k, int32_t ef_search,
+                              const dg_filter* filter, float* out_dist,
+                              int64_t* out_ids);
+dg_status dg_hnsw_after_sync(dg_index* ix);
+// ef_search 0..1024 (else DG_EINVAL), k <= 1024 (else DG_ENOT_SUPPORT): the
+// host form asks before it stages anything
+dg_status dg_hnsw_check_search_args(int32_t k, int32_t ef_search);
+
 // ---- kernel launchers (kernels.hip.cpp; authoritative signatures) ----
 namespace dgk {
+// ---- HNSW (hnsw.hip.cpp) ----
+// the device mirror of a dg_hnsw::Graph (dg_hnsw_core.h), passed by value
+struct hnsw_graph {
+  const float* rows;        // [n][d] f32, d padded to a multiple of 4
+  const int32_t* cnt0;      // level 0: count[n], links[n][maxM0]
+  const uint32_t* links0;
+  const int32_t* levels;    // [n]
+  const int64_t* up_off;    // [n + 1] first list of node i at levels >= 1
+  const int32_t* up_cnt;    // per list
+  const uint32_t* up_links; // per list, maxM slots
+  const uint32_t* pass;     // bit per node: not deleted and passes the filter
+  const int64_t* ids;       // external id per node
+  int64_t n, entry;
+  int32_t d, maxM, maxM0, max_level, metric;
+};
+// dynamic LDS of one k_hnsw_search block (one wave): the query, C and W of
+// ef' packed entries each and the neighbour staging
+size_t hnsw_search_lds(int32_t d, int32_t efp);
+// one wave per query; queries [nq][d_user]; visited = nq * vwords zeroed
+// words (vwords = ceil(n / 32)); counters[2] += (expansions, dist_evals);
+// *flag |= 1 if a wave met a bad link or the iteration cap.  Needs n > 0,
+// 1 <= k <= efp <= 1024.
+void hnsw_search(hipStream_t s, const hnsw_graph& g, const float* queries,
+                 int64_t nq, int32_t d_user, int32_t k, int32_t efp,
+                 uint32_t* visited, int64_t vwords, float* out_dist,
+                 int64_t* out_ids, unsigned long long* counters,
+                 int32_t* flag);
 void probe_unpack(hipStream_t s, const uint64_t* topk, int64_t nq,
                   int32_t nprobe, const uint8_t* mask, int32_t* probes);
 void probes_all(hipStream_t s, int64_t nq, int32_t nprobe,

@@ -451,6 +451,10 @@ extern "C" dg_status dg_sharded_create(dg_sharded** out,
                  dp->kind);
     return DG_ENOT_SUPPORT;
   }
+  if (dg_kind_is_hnsw(dp->kind)) {
+    dg_set_error("a sharded index does not hold DG_INDEX_HNSW");
+    return DG_ENOT_SUPPORT;
+  }
   const int ndev = dg_device_count();
   if (ndev == 0) {
     dg_set_error("no HIP device (the GPU path has no CPU fallback)");

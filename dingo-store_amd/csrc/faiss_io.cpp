@@ -313,6 +313,11 @@ extern "C" dg_status dg_save_faiss(dg_index* ix, const char* path) {
                  "dg_save_faiss_binary");
     return DG_ENOT_SUPPORT;
   }
+  if (dg_kind_is_hnsw(ix->desc.kind)) {
+    dg_set_error("dg_save_faiss called on an HNSW index: use "
+                 "dg_save_hnswlib");
+    return DG_ENOT_SUPPORT;
+  }
   std::shared_lock lk(ix->rw);
   if (ix->storage != DG_STORAGE_F32) {
     dg_set_error("dg_save_faiss: f16 or SQ8 row storage would need a scalar-"

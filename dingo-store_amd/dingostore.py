@@ -17,6 +17,9 @@ L2, IP, COSINE = 0, 1, 2
 FLAT, IVF_FLAT, IVF_PQ = 0, 1, 2
 # binary (Hamming) indexes: d is in bits, rows are np.uint8 [n, d // 8]
 BINARY_FLAT, BINARY_IVF_FLAT = 3, 4
+# graph index: host-built HNSW graph, searched by one kernel (one wave per
+# query); hnsw_configure / set_ef / search_hnsw / save_hnswlib below
+HNSW = 5
 HAMMING = 3
 # row storage of an IVF_FLAT index (dg_storage)
 STORAGE_F32, STORAGE_F16, STORAGE_SQ8 = 0, 1, 2
@@ -32,6 +35,7 @@ def _storage_code(storage):
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
+_i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 
 
 class DgError(RuntimeError):
@@ -67,6 +71,16 @@ class _Stats(C.Structure):
         ("last_scan_bytes_algorithmic", C.c_int64),
         ("last_scan_gbps_algorithmic", C.c_double),
         ("deleted_count", C.c_int64),
+    ]
+
+
+class _HnswInfo(C.Structure):
+    _fields_ = [
+        ("nlinks", C.c_int32), ("max_m0", C.c_int32),
+        ("ef_construction", C.c_int32), ("ef_search", C.c_int32),
+        ("max_level", C.c_int32), ("entry_point", C.c_int64),
+        ("n_nodes", C.c_int64), ("n_deleted", C.c_int64),
+        ("seed", C.c_uint64),
     ]
 
 
@@ -199,6 +213,24 @@ def _load():
     lib.dg_sharded_set_sq_ranges.argtypes = [C.c_void_p, _f32p, _f32p]
     lib.dg_sharded_get_sq_ranges.argtypes = [C.c_void_p, _f32p, _f32p]
     lib.dg_mirror_selftest_sq8.restype = C.c_int
+    # HNSW
+    _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
+    lib.dg_hnsw_configure.argtypes = [C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_uint64]
+    lib.dg_hnsw_set_ef.argtypes = [C.c_void_p, C.c_int32]
+    lib.dg_hnsw_get_info.argtypes = [C.c_void_p, C.POINTER(_HnswInfo)]
+    lib.dg_search_hnsw.argtypes = lib.dg_search.argtypes
+    lib.dg_search_hnsw_device.argtypes = lib.dg_search_device.argtypes
+    lib.dg_hnsw_export_level.argtypes = [C.c_void_p, C.c_int32, _i32p, _u32p]
+    lib.dg_hnsw_export_nodes.argtypes = [C.c_void_p, _i64p, _u8p, _i32p]
+    lib.dg_hnsw_last_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64)]
+    lib.dg_save_hnswlib.argtypes = [C.c_void_p, C.c_char_p]
+    lib.dg_load_hnswlib.argtypes = [C.POINTER(C.c_void_p), C.c_char_p,
+                                    C.c_int32, C.c_int32, C.c_int32]
+    lib.dg_hnsw_max_elements.argtypes = [C.c_void_p, C.c_int64]
+    lib.dg_hnsw_max_elements.restype = C.c_int64
+    lib.dg_mirror_selftest_hnsw.restype = C.c_int
     return lib
 
 
@@ -595,6 +627,91 @@ class Index:
 
     def sync(self):
         _check(lib().dg_sync(self.h), "dg_sync")
+
+    # ---- HNSW (kind HNSW) ----
+    def hnsw_configure(self, nlinks=32, ef_construction=200, seed=100):
+        """Graph parameters, only while the index is empty
+        (dg_hnsw_configure): nlinks 2..128, ef_construction 1..4096."""
+        _check(lib().dg_hnsw_configure(self.h, nlinks, ef_construction, seed),
+               "dg_hnsw_configure")
+
+    def set_ef(self, ef_search):
+        """The stored ef_search (1..1024) that search() and ef_search = 0
+        use (dg_hnsw_set_ef)."""
+        _check(lib().dg_hnsw_set_ef(self.h, ef_search), "dg_hnsw_set_ef")
+
+    def hnsw_info(self):
+        s = _HnswInfo()
+        _check(lib().dg_hnsw_get_info(self.h, C.byref(s)),
+               "dg_hnsw_get_info")
+        return {f[0]: getattr(s, f[0]) for f in _HnswInfo._fields_}
+
+    def search_hnsw(self, queries, k, ef_search=0, filt=None):
+        """Graph search with a beam of max(ef_search, k); ef_search 0 = the
+        stored value.  Returns (dist, ids) like search()."""
+        q = np.ascontiguousarray(queries, np.float32)
+        nq = q.shape[0]
+        dist = np.empty((nq, max(k, 0)), np.float32)
+        ids = np.empty((nq, max(k, 0)), np.int64)
+        fp = C.byref(filt) if filt is not None else None
+        _check(lib().dg_search_hnsw(self.h, nq, q, k, ef_search, fp, dist,
+                                    ids), "dg_search_hnsw")
+        return dist, ids
+
+    def search_hnsw_device(self, q_ptr, nq, k, ef_search, dist_ptr, ids_ptr,
+                           filt=None):
+        """Device-pointer form, no synchronisation (sync() waits)."""
+        fp = C.byref(filt) if filt is not None else None
+        _check(lib().dg_search_hnsw_device(
+            self.h, nq, C.c_void_p(q_ptr), k, ef_search, fp,
+            C.c_void_p(dist_ptr), C.c_void_p(ids_ptr)),
+            "dg_search_hnsw_device")
+
+    def hnsw_export(self):
+        """The graph as the DEVICE holds it: dict(ids, deleted, levels,
+        counts, links, entry_point, max_level, nlinks); counts[l] is [n]
+        int32 (-1: the node has no level l), links[l] is [n, cap(l)] uint32,
+        for l = 0 .. max_level (dg_hnsw_export_nodes / _level)."""
+        info = self.hnsw_info()
+        n = info["n_nodes"]
+        ids = np.zeros(n, np.int64)
+        deleted = np.zeros(n, np.uint8)
+        levels = np.zeros(n, np.int32)
+        _check(lib().dg_hnsw_export_nodes(self.h, ids, deleted, levels),
+               "dg_hnsw_export_nodes")
+        counts, links = [], []
+        for level in range(max(info["max_level"], 0) + 1):
+            cap = info["max_m0"] if level == 0 else info["nlinks"]
+            c = np.zeros(n, np.int32)
+            lk = np.zeros((n, cap), np.uint32)
+            _check(lib().dg_hnsw_export_level(self.h, level, c, lk),
+                   "dg_hnsw_export_level")
+            counts.append(c)
+            links.append(lk)
+        return dict(ids=ids, deleted=deleted, levels=levels, counts=counts,
+                    links=links, entry_point=info["entry_point"],
+                    max_level=info["max_level"], nlinks=info["nlinks"])
+
+    def hnsw_last_counters(self):
+        """(expansions, dist_evals) summed over the last search's batch."""
+        a, b = C.c_int64(), C.c_int64()
+        _check(lib().dg_hnsw_last_counters(self.h, C.byref(a), C.byref(b)),
+               "dg_hnsw_last_counters")
+        return a.value, b.value
+
+    def save_hnswlib(self, path):
+        """hnswlib's saveIndex container (what the reference's HNSW
+        snapshots are)."""
+        _check(lib().dg_save_hnswlib(self.h, path.encode()),
+               "dg_save_hnswlib")
+
+    @classmethod
+    def load_hnswlib(cls, path, metric, d, device=-1):
+        """The file carries neither metric nor d: pass both."""
+        h = C.c_void_p()
+        _check(lib().dg_load_hnswlib(C.byref(h), path.encode(), metric, d,
+                                     device), "dg_load_hnswlib")
+        return cls._from_handle(h)
 
     def set_list_mask(self, mask):
         if mask is None:

@@ -526,6 +526,131 @@ class GpuIvfPqIndex : public GpuIndexBase {
   }
 };
 
+// VectorIndexHnsw (vector_index_hnsw.cc) over DG_INDEX_HNSW.  The overrides
+// restate the reference's: Add is Upsert (:196), Delete of a missing id is
+// EINTERNAL, the element count that IsExceedsMaxElements, NeedToRebuild and
+// NeedToSave reason about is hnswlib's getCurrentElementCount, which counts
+// deleted nodes (:531-610), Save / Load speak hnswlib's saveIndex container.
+class GpuHnswIndex : public GpuIndexBase {
+ public:
+  GpuHnswIndex(MetricType m, int32_t d, int32_t nlinks, int32_t efc,
+               int64_t max_elements, int dev)
+      : GpuIndexBase(DG_INDEX_HNSW, m, d, 0, dev),
+        max_elements_(max_elements), device_(dev) {
+    if (create_st_ == DG_OK)
+      create_st_ = dg_hnsw_configure(idx_, nlinks, efc, 100);
+    if (create_st_ == DG_OK) dg_hnsw_max_elements(idx_, max_elements);
+  }
+  bool NeedTrain() override { return false; }
+  Status Add(const std::vector<VectorWithId>& v) override {
+    return Upsert(v);
+  }
+  Status Delete(const std::vector<int64_t>& ids) override {
+    Status s = GpuIndexBase::Delete(ids);
+    if (s.code == kEVectorInvalid) s.code = kEInternal;
+    return s;
+  }
+  bool IsExceedsMaxElements(int64_t vector_size) override {
+    dg_hnsw_info info{};
+    if (dg_hnsw_get_info(idx_, &info) != DG_OK) return true;
+    return info.n_nodes + vector_size > max_elements_;
+  }
+  bool NeedToRebuild() override {
+    dg_hnsw_info info{};
+    if (dg_hnsw_get_info(idx_, &info) != DG_OK) return false;
+    if (info.n_nodes == 0 || info.n_deleted == 0) return false;
+    return info.n_deleted > info.n_nodes / 2;
+  }
+  bool NeedToSave(int64_t last_save_log_behind) override {
+    dg_hnsw_info info{};
+    if (dg_hnsw_get_info(idx_, &info) != DG_OK || info.n_nodes == 0)
+      return false;
+    return last_save_log_behind > kNeedSaveCount;  // hnsw_need_save_count
+  }
+  bool SupportSave() override { return true; }
+  Status Save(const std::string& path) override {
+    return from_dg(dg_save_hnswlib(idx_, path.c_str()));
+  }
+  Status Load(const std::string& path) override {
+    dg_hnsw_info info{};
+    dg_status st = dg_hnsw_get_info(idx_, &info);
+    if (st != DG_OK) return from_dg(st);
+    dg_index* ni = nullptr;
+    st = dg_load_hnswlib(&ni, path.c_str(), (int32_t)metric_, dim_, device_);
+    if (st != DG_OK) return from_dg(st);
+    (void)dg_hnsw_set_ef(ni, info.ef_search);
+    // the limit is this index's parameter, as in the reference's loading
+    // constructor, not the file's
+    dg_hnsw_max_elements(ni, max_elements_);
+    dg_index_destroy(idx_);
+    idx_ = ni;
+    if (batching_) return EnableBatching(batch_opts_.max_batch,
+                                         batch_opts_.max_wait_us);
+    return Status::OK();
+  }
+  Status Search(const std::vector<VectorWithId>& queries, uint32_t topk,
+                const std::vector<std::shared_ptr<FilterFunctor>>& filters,
+                bool reconstruct, const VectorSearchParameter& p,
+                std::vector<VectorWithDistanceResult>& results) override {
+    if (queries.empty())
+      return {kEillegalParamteters, "vector_with_ids is empty"};
+    if (topk == 0) return Status::OK();
+    // vector_index_hnsw.cc:332
+    if (p.hnsw_efsearch < 0 || p.hnsw_efsearch > 1024)
+      return {kEillegalParamteters, "efsearch is illegal"};
+    std::vector<float> x;
+    std::vector<int64_t> ids;
+    Status s = pack(queries, dim_, x, ids);
+    if (!s.ok()) return s;
+    dg_filter df{};
+    dg_filter* dfp = nullptr;
+    if (!filters.empty()) {
+      if (filters.size() == 1 && filters[0]->ToDeviceFilter(&df)) dfp = &df;
+      else return {kEVectorNotSupport, "composite filters via reader fallback"};
+    }
+    std::vector<float> dist((size_t)queries.size() * topk);
+    std::vector<int64_t> labels((size_t)queries.size() * topk, -1);
+    dg_status st = dg_search_hnsw(idx_, (int64_t)queries.size(), x.data(),
+                                  (int32_t)topk, p.hnsw_efsearch, dfp,
+                                  dist.data(), labels.data());
+    if (st != DG_OK) return from_dg(st);
+    results.clear();
+    results.resize(queries.size());
+    std::vector<int64_t> found;
+    for (size_t row = 0; row < queries.size(); row++)
+      for (uint32_t i = 0; i < topk; i++) {
+        const size_t pos = row * topk + i;
+        if (labels[pos] < 0) continue;
+        VectorWithDistance vd;
+        vd.vector_with_id.id = labels[pos];
+        vd.vector_with_id.vector.dimension = dim_;
+        vd.metric_type = metric_;
+        vd.distance =
+            metric_ == MetricType::kL2 ? dist[pos] : 1.0f - dist[pos];
+        results[row].vector_with_distances.push_back(std::move(vd));
+        found.push_back(labels[pos]);
+      }
+    if (reconstruct && !found.empty()) {  // with_vector_data
+      std::vector<float> rows(found.size() * (size_t)dim_);
+      st = dg_reconstruct(idx_, (int64_t)found.size(), found.data(),
+                          rows.data());
+      if (st != DG_OK) return from_dg(st);
+      size_t at = 0;
+      for (auto& r : results)
+        for (auto& vd : r.vector_with_distances) {
+          vd.vector_with_id.vector.float_values.assign(
+              rows.begin() + at * dim_, rows.begin() + (at + 1) * dim_);
+          at++;
+        }
+    }
+    return Status::OK();
+  }
+
+ private:
+  int64_t max_elements_;
+  int device_;  // as given to the factory (-1 = the current device)
+};
+
 // An index whose parameters the GPU library refuses (DG_ENOT_SUPPORT at
 // create): every operation answers EVECTOR_NOT_SUPPORT, which is what sends
 // the reader to its brute-force scan (SearchWithBruteForceFallback).
@@ -925,6 +1050,16 @@ std::unique_ptr<VectorIndex> NewIvfPqIndex(MetricType metric, int32_t dim,
   if (s.code == kEVectorNotSupport)
     return std::make_unique<GpuUnsupportedIndex>(metric, dim, s.msg);
   if (!s.ok()) return nullptr;
+  return p;
+}
+
+std::unique_ptr<VectorIndex> NewHnswIndex(MetricType metric, int32_t dim,
+                                          int32_t nlinks,
+                                          int32_t efconstruction,
+                                          int64_t max_elements, int device) {
+  auto p = std::make_unique<GpuHnswIndex>(metric, dim, nlinks, efconstruction,
+                                          max_elements, device);
+  if (!p->CreateStatus().ok()) return nullptr;
   return p;
 }
 
@@ -1768,6 +1903,132 @@ extern "C" int dg_mirror_selftest_sq8(void) {
         return 423;
     }
   }
+  return 0;
+}
+
+extern "C" int dg_mirror_selftest_hnsw(void) {
+  using namespace dingogpu;
+  if (dg_device_count() == 0) return 1;
+  const int d = 12, n = 500;
+  std::vector<VectorWithId> batch(n);
+  uint32_t s = 4242;
+  for (int i = 0; i < n; i++) {
+    batch[i].id = i * 2 + 5;
+    batch[i].vector.dimension = d;
+    batch[i].vector.float_values.resize(d);
+    for (int j = 0; j < d; j++) {
+      s = s * 1664525u + 1013904223u;
+      batch[i].vector.float_values[j] = (float)((int)(s >> 24) % 9 - 4);
+    }
+    batch[i].vector.float_values[i % d] += 0.25f * (float)(i / d + 1);
+  }
+  VectorSearchParameter p;
+  p.hnsw_efsearch = 64;
+  for (MetricType metric : {MetricType::kL2, MetricType::kInnerProduct}) {
+    auto idx = NewHnswIndex(metric, d, 8, 100, 1000, -1);
+    if (!idx) return 500;
+    if (!idx->IsTrained() || idx->NeedTrain() || !idx->SupportSave())
+      return 501;
+    if (idx->NeedToSave(20000)) return 502;  // empty
+    if (!idx->Add(batch).ok()) return 503;
+    if (!idx->Add({batch[3]}).ok()) return 504;  // Add is Upsert
+    int64_t cnt = 0, del = 0;
+    if (!idx->GetCount(cnt).ok() || cnt != n) return 505;
+    if (!idx->GetDeletedCount(del).ok() || del != 1) return 506;
+    if (idx->IsExceedsMaxElements(499) || !idx->IsExceedsMaxElements(500))
+      return 507;  // 501 nodes of 1000
+    if (!idx->NeedToSave(20000) || idx->NeedToSave(10)) return 508;
+    std::vector<VectorWithId> queries(batch.begin(), batch.begin() + 30);
+    std::vector<VectorWithDistanceResult> before, after, filtered;
+    if (!idx->Search(queries, 4, {}, true, p, before).ok()) return 509;
+    if (before.size() != queries.size()) return 510;
+    if (metric == MetricType::kL2)
+      for (size_t i = 0; i < queries.size(); i++) {
+        auto& r = before[i].vector_with_distances;
+        if (r.size() != 4) return 511;
+        if (r[0].vector_with_id.id != queries[i].id || r[0].distance != 0.f)
+          return 512;
+        if (r[0].vector_with_id.vector.float_values !=
+            queries[i].vector.float_values)
+          return 513;  // with_vector_data
+        for (size_t j = 1; j < r.size(); j++)
+          if (r[j].distance < r[j - 1].distance) return 514;
+      }
+    else  // the reported distance is 1 - score, ascending
+      for (size_t i = 0; i < queries.size(); i++) {
+        auto& r = before[i].vector_with_distances;
+        if (r.size() != 4) return 515;
+        for (size_t j = 0; j < r.size(); j++) {
+          float dot = 0.f;
+          for (int t = 0; t < d; t++)
+            dot += queries[i].vector.float_values[t] *
+                   r[j].vector_with_id.vector.float_values[t];
+          if (std::fabs(r[j].distance - (1.0f - dot)) >
+              1e-4f * (1.0f + std::fabs(dot)))
+            return 516;
+          if (j && r[j].distance < r[j - 1].distance) return 517;
+        }
+      }
+    // a range filter holds for every answer
+    auto f = std::make_shared<RangeFilterFunctor>(100, 300);
+    if (!idx->Search(queries, 4, {f}, false, p, filtered).ok()) return 518;
+    for (auto& r : filtered) {
+      if (r.vector_with_distances.size() != 4) return 519;
+      for (auto& vd : r.vector_with_distances)
+        if (vd.vector_with_id.id < 100 || vd.vector_with_id.id >= 300)
+          return 520;
+    }
+    VectorSearchParameter bad = p;
+    bad.hnsw_efsearch = 1025;
+    if (idx->Search(queries, 4, {}, false, bad, after).code !=
+        kEillegalParamteters)
+      return 521;
+    std::vector<VectorWithDistanceResult> rr;
+    if (idx->RangeSearch(queries, 1.0f, {}, false, p, rr).code !=
+        kEVectorNotSupport)
+      return 522;
+    // Delete: a missing id is EINTERNAL and removes nothing
+    if (idx->Delete({batch[0].id, 999999}).code != kEInternal) return 523;
+    if (!idx->GetCount(cnt).ok() || cnt != n) return 524;
+    if (!idx->Delete({batch[0].id}).ok()) return 525;
+    std::vector<VectorWithDistanceResult> gone;
+    if (!idx->Search({batch[0]}, 4, {}, false, p, gone).ok()) return 526;
+    for (auto& vd : gone[0].vector_with_distances)
+      if (vd.vector_with_id.id == batch[0].id) return 527;
+    if (idx->NeedToRebuild()) return 528;  // 2 deleted of 501
+    // Save (hnswlib container) -> Load -> the same answers
+    if (!idx->Search(queries, 4, {}, false, p, before).ok()) return 529;
+    const std::string path = "/tmp/dg_mirror_selftest_hnsw." +
+                             std::to_string((long)getpid()) + ".bin";
+    if (!idx->Save(path).ok()) return 530;
+    auto fresh = NewHnswIndex(metric, d, 8, 100, 1000, -1);
+    Status ls = fresh ? fresh->Load(path) : Status{kEInternal, "create"};
+    auto wrong = NewHnswIndex(metric, d + 1, 8, 100, 1000, -1);
+    const bool refused = wrong && !wrong->Load(path).ok();
+    remove(path.c_str());
+    if (!ls.ok()) return 531;
+    if (!refused) return 532;
+    if (!fresh->GetCount(cnt).ok() || cnt != n - 1) return 533;
+    if (!fresh->GetDeletedCount(del).ok() || del != 2) return 534;
+    if (!fresh->Search(queries, 4, {}, false, p, after).ok()) return 535;
+    if (after.size() != before.size()) return 536;
+    for (size_t i = 0; i < before.size(); i++) {
+      auto& a = before[i].vector_with_distances;
+      auto& b = after[i].vector_with_distances;
+      if (a.size() != b.size()) return 537;
+      for (size_t j = 0; j < a.size(); j++)
+        if (a[j].distance != b[j].distance ||
+            a[j].vector_with_id.id != b[j].vector_with_id.id)
+          return 538;
+    }
+    // more than half deleted: rebuild
+    std::vector<int64_t> half;
+    for (int i = 1; i <= 260; i++) half.push_back(batch[i].id);
+    if (!fresh->Delete(half).ok()) return 539;
+    if (!fresh->NeedToRebuild()) return 540;
+  }
+  // a geometry the library refuses
+  if (NewHnswIndex(MetricType::kL2, d, 1, 100, 1000, -1)) return 541;
   return 0;
 }
 

@@ -60,6 +60,7 @@ struct VectorSearchParameter {
   int32_t ivf_flat_nprobe = 0;  // parameter.ivf_flat().nprobe()
   int32_t ivf_pq_nprobe = 0;
   int32_t binary_ivf_flat_nprobe = 0;  // parameter.binary_ivf_flat().nprobe()
+  int32_t hnsw_efsearch = 0;  // parameter.hnsw().efsearch(); 0 = the index's
   bool enable_range_search = false;
   float radius = 0.f;
 };
@@ -275,6 +276,23 @@ std::unique_ptr<VectorIndex> NewBinaryIvfFlatIndex(int32_t dim,
                                                    int32_t ncentroids,
                                                    int device = -1);
 
+// HNSW (VectorIndexHnsw, vector_index_hnsw.cc): a host-built graph searched
+// on the GPU, metric L2 / inner product / cosine.  Add is Upsert, Delete of a
+// missing id is EINTERNAL, Delete marks (hnswlib markDelete) and an Upsert of
+// a present id marks the old node and inserts a new one, so the element count
+// behind IsExceedsMaxElements (count + vector_size > max_elements) and
+// NeedToRebuild (deleted above half of it) includes marked nodes.  Search
+// reads hnsw_efsearch (0..1024, else EILLEGAL_PARAMTETERS; 0 = the index's
+// stored value) and fills float_values when reconstruct is set; RangeSearch
+// answers EVECTOR_NOT_SUPPORT.  Save / Load speak hnswlib's saveIndex
+// container; Load takes metric and dimension from this index.  nullptr if
+// the library refuses the parameters (nlinks 2..128, efconstruction 1..4096).
+std::unique_ptr<VectorIndex> NewHnswIndex(MetricType metric, int32_t dim,
+                                          int32_t nlinks,
+                                          int32_t efconstruction,
+                                          int64_t max_elements,
+                                          int device = -1);
+
 // Search batching (off by default).  The reference's search pool calls
 // Search from 16 threads with one query each (vector_index.cc:53-54,244-271)
 // and one index runs one search at a time.  With batching on, Search of a
@@ -350,6 +368,12 @@ int dg_mirror_selftest_f16(void);
 // Save -> Load into a fresh SQ8 index (an f16 index refuses the file) -> the
 // same top-4, bit for bit.
 int dg_mirror_selftest_sq8(void);
+// NewHnswIndex through the mirror, L2 and inner product: Add (an Upsert) ->
+// counts and the max-elements / save / rebuild rules -> self top-1 at
+// distance 0 with the stored vector returned, the 1 - score flip -> a range
+// filter -> the efsearch bound -> Delete contracts -> Save -> Load (a wrong
+// dimension refused) -> the same top-4, bit for bit.
+int dg_mirror_selftest_hnsw(void);
 // The second driver of tools/bench_concurrent.py, free of Python threads:
 // `threads` std::threads search the rows of q ([nq x d] float32) round-robin
 // through dg_search (batched = 0) or dg_search_batched, one query per call,

@@ -65,9 +65,11 @@ typedef enum dg_index_kind {
   DG_INDEX_BINARY_FLAT = 3,     /* VectorIndexFlat<faiss::IndexBinary,
                                    IndexBinaryIDMap2>,
                                    src/vector/vector_index_flat.cc:71,99-102 */
-  DG_INDEX_BINARY_IVF_FLAT = 4  /* VectorIndexIvfFlat<faiss::IndexBinary,
+  DG_INDEX_BINARY_IVF_FLAT = 4, /* VectorIndexIvfFlat<faiss::IndexBinary,
                                    IndexBinaryIVF>,
                                    src/vector/vector_index_ivf_flat.cc:62,75-80 */
+  DG_INDEX_HNSW = 5      /* VectorIndexHnsw over hnswlib,
+                            src/vector/vector_index_hnsw.cc ("HNSW" below) */
 } dg_index_kind;
 
 typedef enum dg_metric {
@@ -488,6 +490,92 @@ dg_status dg_range_search_binary(dg_index* idx, int64_t nq, const uint8_t* x,
 dg_status dg_save_faiss_binary(dg_index* idx, const char* path);
 dg_status dg_load_faiss_binary(dg_index** out, const char* path,
                                int32_t device);
+
+/* ---- HNSW (DG_INDEX_HNSW; float vectors, L2 / IP / COSINE) ----
+ * The graph is built on the host, one thread, by hnswlib's insertion
+ * algorithm with a counter-based level draw (a build is a function of the
+ * rows, their order and the seed); rows are held on the host as well as on
+ * the device (the build reads them).  The graph is mirrored on the device
+ * before the first search after a mutation and every search runs in one
+ * kernel, one wave per query (HNSW, has the search definition).
+ * dg_index_desc is unchanged: nlist, pq_m and pq_nbits are ignored.
+ *  - defaults: nlinks 32, ef_construction 200, ef_search 10 (hnswlib's),
+ *    seed 100 (vector_index_hnsw.cc:181-182).  dg_hnsw_configure only while
+ *    the index is empty (else DG_EINVAL); nlinks 2..128 and ef_construction
+ *    1..4096, else DG_ENOT_SUPPORT.
+ *  - search: ef_search 0..1024 (vector_index_hnsw.cc:332), else DG_EINVAL;
+ *    0 = the stored value (dg_hnsw_set_ef, 1..1024).  The beam is max(ef, k)
+ *    wide.  k > 1024 is DG_ENOT_SUPPORT, k <= 0 an OK no-op, an empty index
+ *    answers all -1.  Distances: L2 raw squared distance, IP / COSINE raw
+ *    score; pads -1 / 0.0.  Every filter kind and negation apply.  dg_search
+ *    / dg_search_device are dg_search_hnsw with ef_search = 0 (nprobe is
+ *    ignored); dg_search_batched runs dg_search and counts the call as
+ *    bypassed.  COSINE normalises rows and queries as the reference's HNSW
+ *    does, x / (sqrtf(sum x^2) + 1e-30f), not with the 1e-5 window of the
+ *    faiss kinds.  The _device form does not synchronise; a wave that meets
+ *    a corrupt link or its iteration cap raises a flag that the host form,
+ *    dg_hnsw_last_counters and dg_stats report as DG_EINTERNAL.
+ *  - add / upsert / remove follow Flat: a negative id (DG_EINVAL), an id
+ *    repeated in the call or (add) present (DG_EID_DUPLICATED), a NaN or
+ *    infinite component (DG_EINVAL) and a remove with a missing id
+ *    (DG_ENOT_FOUND) fail the whole call before anything moves.  Remove is
+ *    hnswlib's markDelete: the node stays, is traversed, is never returned.
+ *    Upsert of a present id marks the old node deleted and inserts a new
+ *    one (hnswlib updates in place; the id answers with the new vector
+ *    either way), so n_nodes grows with every upsert until a rebuild.
+ *  - dg_train is an OK no-op, dg_reconstruct works, dg_add_device downloads
+ *    the rows.  DG_ENOT_SUPPORT: dg_range_search, dg_save / dg_load,
+ *    dg_save_faiss, dg_set_storage other than F32, dg_set_list_mask,
+ *    dg_sharded_create.  The binary calls answer DG_EINVAL.
+ *  - dg_stats: last_scan_ms is the search kernel's time (a batch so large
+ *    that its visited bitmaps exceed 256 MB runs as several launches, and
+ *    the clears of that workspace between them are then counted too),
+ *    last_scan_bytes_algorithmic = dist_evals * 4 * d, device_bytes counts
+ *    rows and graph.
+ *  - dg_hnsw_export_* read the DEVICE copy back.  export_level: counts[i] =
+ *    -1 where node i has no such level, links [n_nodes x cap(level)], cap =
+ *    2 * nlinks on level 0 and nlinks above; level > max_level: DG_EINVAL.
+ *  - dg_hnsw_last_counters: expansions (level-0 pops) and dist_evals (keys
+ *    computed, on every level, the entry point's included) summed over the
+ *    last search's batch; waits for the stream.
+ *  - dg_save_hnswlib / dg_load_hnswlib: hnswlib's saveIndex container
+ *    (0.7.x / 0.8.x layout), deleted nodes written with their
+ *    mark.  The file carries neither metric nor d: the caller passes both
+ *    (COSINE files hold normalised rows).  Malformed content is DG_EIO, an M
+ *    outside 2..128 DG_ENOT_SUPPORT; the file is checked completely before
+ *    the first device call. */
+typedef struct dg_hnsw_info {
+  int32_t nlinks, max_m0, ef_construction, ef_search, max_level;
+  int64_t entry_point; /* internal node, -1 if empty */
+  int64_t n_nodes;     /* tombstoned included */
+  int64_t n_deleted;
+  uint64_t seed;
+} dg_hnsw_info;
+dg_status dg_hnsw_configure(dg_index* idx, int32_t nlinks,
+                            int32_t ef_construction, uint64_t seed);
+dg_status dg_hnsw_set_ef(dg_index* idx, int32_t ef_search);
+dg_status dg_hnsw_get_info(dg_index* idx, dg_hnsw_info* out);
+dg_status dg_search_hnsw(dg_index* idx, int64_t nq, const float* x, int32_t k,
+                         int32_t ef_search, const dg_filter* filter,
+                         float* out_dist, int64_t* out_ids);
+dg_status dg_search_hnsw_device(dg_index* idx, int64_t nq, const float* d_x,
+                                int32_t k, int32_t ef_search,
+                                const dg_filter* filter, float* d_out_dist,
+                                int64_t* d_out_ids);
+dg_status dg_hnsw_export_level(dg_index* idx, int32_t level, int32_t* counts,
+                               uint32_t* links);
+dg_status dg_hnsw_export_nodes(dg_index* idx, int64_t* ids, uint8_t* deleted,
+                               int32_t* levels);
+dg_status dg_hnsw_last_counters(dg_index* idx, int64_t* expansions,
+                                int64_t* dist_evals);
+dg_status dg_save_hnswlib(dg_index* idx, const char* path);
+dg_status dg_load_hnswlib(dg_index** out, const char* path, int32_t metric,
+                          int32_t d, int32_t device);
+/* The container's max_elements field (hnswlib's capacity; this library grows
+ * on demand and only carries the number): set >= 0 stores it, set < 0 only
+ * reads.  Returns the stored value, 0 = "the node count at save"; -1 if idx
+ * is not an HNSW index.  dg_load_hnswlib takes it from the file. */
+int64_t dg_hnsw_max_elements(dg_index* idx, int64_t set);
 
 /* ---- multi-GPU sharding support ----
  * Each rank holds a shard of the database (row-sharded)
